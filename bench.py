@@ -2,17 +2,26 @@
 """Headline benchmark: denoising TRAINING steps/sec (fwd + bwd + grad-clip + AdamW) of PixArt-Sigma-XL/2 at 1024px,
 batch 16 per GPU, data-parallel over N GPUs of one node (BASELINE.json `metric`, configs[2]).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One JSON line on rank 0.  A "step" = q_sample -> PixArtMS.forward -> IDDPM loss (MSE + VB) -> backward (gradient all-reduce
 overlapped) -> global-norm clip -> AdamW, on synthetic latents / caption features already resident in HBM, random-init
 weights with the zero-init tensors re-randomised.  `value` is whole-job steps/s x nothing: every
 rank does one step of batch 16, so steps/s of the job = 1 / (max-over-ranks step time) and images/s = 16 N x that.
+`ms_per_step` is the wall time of one of the K timed steps.
 
-Extra objects: `roofline` (MFMA bound; algorithmic FLOPs of SURVEY.md section 8d / time; the dominant kernel measured live with
-events on the launch stream) and `cpu_baseline` (oracle/ = CPU port of the reference, timed on the host cores on a
-bounded sample).
+A plain run sets up, warms up, times K steps and prints the line; its `roofline` is the whole step's (algorithmic FLOPs of
+SURVEY.md section 8d / time, computed from shapes).  --full adds the legs that take runs of their own (N = 1 only): the
+dominant kernel and the other per-kernel figures measured live with events on the launch stream, the MFMA-only rate probe,
+the other operand build (`other_dtype`), the stock PyTorch-ROCm step (`torch_rocm_baseline`), BASELINE configs 2 / 4 / 5
+(`configs`) and `cpu_baseline` (oracle/ = CPU port of the reference, timed on the host cores on a bounded sample); the
+--no-* options drop single legs of a --full run.
+
+--dump-outputs DIR writes, after the timed steps, what the last step computed as float32 .npy files (rank 0's, ~8 MB):
+the per-sample loss terms, the unscaled gradient norm, the loss scale, and a fixed seeded sample of the updated fp32
+master weights and of the gradient buffer (DUMP_SAMPLE flat indices; the gradients as they stand in the buffer, i.e.
+multiplied by the loss scale on the fp16 build).  Inputs and weights are seeded, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -30,6 +39,26 @@ sys.path.insert(0, ROOT)
 
 D, H, DFF, DEPTH, LTXT = 1152, 16, 4608, 28, 300
 MFMA_PEAK = 2.5e15   # dense bf16, MI355X (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 20   # flat indices sampled from the master weights / gradient buffer by --dump-outputs (4 MB each as float32)
+
+
+def dump_outputs(out_dir, terms, opt, scaler):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files (see the module docstring).  Runs after the timed region."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    st = opt.store
+    g = torch.Generator(device="cpu").manual_seed(20240)
+    idx = torch.randint(0, st.total, (min(DUMP_SAMPLE, st.total),), generator=g).sort().values.to(st.master.device)
+    arrays = {k: terms[k] for k in ("loss", "mse", "vb")}
+    arrays["grad_norm"] = opt.last_norm.reshape(1)
+    arrays["loss_scale"] = torch.tensor([scaler.value if scaler is not None else 1.0])
+    arrays["params_sample"] = st.master[idx]
+    arrays["grads_sample"] = st.grad[idx]
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().float().cpu().numpy())
+    return sorted(arrays)
+
+
 def _pmc_files():
     """profiles/*_pmc_attention.json, newest session first (tools/pmc_query.py --json; name order: round, then `final` over numbered / lettered sessions)."""
     import glob
@@ -339,6 +368,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=16, help="per-GPU batch (BASELINE: 16)")
     ap.add_argument("--image-size", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own (N = 1 only): per-kernel rooflines and the MFMA-only rate probe, the other operand "
+                         "build, the stock PyTorch-ROCm step, BASELINE configs 2 / 4 / 5 and the CPU baseline; the --no-* options drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32; see the module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-roofline", action="store_true")
     ap.add_argument("--grad-checkpoint", action="store_true")
@@ -355,6 +389,8 @@ def main():
     ap.add_argument("--optimizer", choices=["adamw", "came"], default="adamw",
                     help="adamw = the BASELINE config (configs/PixArt_xl2_internal.py); came = the CAMEWrapper of the Sigma configs")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.dtype == "fp16":                      # must be decided before pixart_sigma_amd is imported: one library per operand type
         os.environ["PXA_OPERAND_DTYPE"] = "f16"
 
@@ -411,7 +447,7 @@ def main():
         loss = terms["loss"].mean()
         (scaler.scale(loss) if scaler is not None else loss).backward()
         opt.step()
-        return loss
+        return loss, terms
 
     def barrier():
         if use_pg:
@@ -423,7 +459,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        loss, terms = step()
     barrier()
     dt = time.perf_counter() - t0
     if use_pg:
@@ -432,6 +468,8 @@ def main():
         dt = tt.item()
     sec_per_step = dt / a.steps
     loss_v = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, terms, opt, scaler)
 
     if rank == 0:
         flops_step = 3 * fwd_flops_per_sample(N) * B          # per GPU, fwd + bwd, no recompute, no optimizer
@@ -453,7 +491,8 @@ def main():
         }
         roof = {"bound": "mfma", "achieved": flops_step / sec_per_step / 1e12, "peak": MFMA_PEAK / 1e12, "unit": "TFLOP/s",
                 "frac": flops_step / sec_per_step / MFMA_PEAK, "traffic": None, "scope": "whole training step (algorithmic FLOPs / wall time)"}
-        if not a.no_kernel_roofline and a.image_size == 1024 and world == 1:   # per-kernel measurements and the CPU leg: N = 1 only
+        legs = a.full and world == 1                 # the --full legs: N = 1 only
+        if legs and not a.no_kernel_roofline and a.image_size == 1024:
             ks = kernel_rooflines(B, N)
             # dominant kernel of the step by total time (profiles/: attn_bwd_dkv_kernel, 56 launches, ~17 % of the step)
             dom = ks["attn_bwd_dkv_kernel"]
@@ -470,7 +509,7 @@ def main():
         issued = issued_flops_per_step(B, N)
         roof["issued_flops_per_step"] = issued
         roof["issued_over_algorithmic"] = issued / flops_step
-        if not a.no_kernel_roofline and a.image_size == 1024 and world == 1:
+        if legs and not a.no_kernel_roofline and a.image_size == 1024:
             try:
                 mr = mfma_only_rate()
                 roof["mfma_only_rate"] = {"TFLOP/s": round(mr[32] / 1e12, 1), "frac_of_peak": round(mr[32] / MFMA_PEAK, 4),
@@ -486,12 +525,12 @@ def main():
         out["roofline"] = roof
         if getattr(opt.reducer, "last_trace", None) is not None:     # PXA_DP_TRACE=1: the last step's per-bucket record (ready / passed / exposed communication)
             out["dp_trace"] = opt.reducer.last_trace
-        if world == 1 and not (a.no_other_dtype and a.no_torch_baseline and a.no_configs):
+        if legs and not (a.no_other_dtype and a.no_torch_baseline and a.no_configs):
             del opt
             model._store = model._engine = None
             del model
             torch.cuda.empty_cache()
-        if world == 1 and not a.no_other_dtype:
+        if legs and not a.no_other_dtype:
             # the other operand build on the same box, same step, same K / W, as its own process (one library per operand type and process)
             import subprocess
             other = "bf16" if a.dtype == "fp16" else "fp16"
@@ -508,7 +547,7 @@ def main():
                 out["other_dtype"]["frac"] = oj["roofline"]["frac"]
             except Exception as e:   # noqa: BLE001
                 out["other_dtype"] = {"dtype": other, "value": None, "error": f"{type(e).__name__}: {e}"[:300]}
-        if not a.no_torch_baseline and world == 1:
+        if legs and not a.no_torch_baseline:
             try:
                 tdt, ckpt = torch_rocm_baseline(B, lat, a.image_size)
                 out["torch_rocm_baseline"] = {"value": 1.0 / tdt, "unit": "steps/s", "ms_per_step": tdt * 1e3, "speedup_of_this_repo": tdt / sec_per_step,
@@ -517,9 +556,9 @@ def main():
                                                       f"{B}" + ("; per-block activation checkpointing (activations did not fit)" if ckpt else "; no recompute")}
             except Exception as e:   # noqa: BLE001 - the baseline leg must never take the headline number down with it
                 out["torch_rocm_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
-        if not a.no_configs and world == 1:
+        if legs and not a.no_configs:
             out["configs"] = baseline_configs()
-        if not a.no_cpu_baseline and world == 1:
+        if legs and not a.no_cpu_baseline:
             cdt, cores, desc, ctimes = cpu_baseline(a.image_size)
             out["cpu_baseline"] = {"value": 1.0 / (cdt * B), "unit": "steps/s", "cores": cores, "kind": "port",
                                    "sample": desc + f"; x{B} per sample to the {a.image_size}px batch-{B} step (samples are independent)",

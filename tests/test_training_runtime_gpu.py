@@ -74,24 +74,26 @@ def test_came_skips_on_overflow():
     assert sc.found_inf and sc.value == 512.0 and torch.equal(m._store.master, w1)
 
 
-def _bench(extra_env, launcher):
+def _bench(extra_env, launcher, dump=None):
     env = dict(os.environ, **extra_env)
     cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--image-size", "256", "--batch", "4",
                       "--no-cpu-baseline", "--no-kernel-roofline", "--no-torch-baseline", "--no-other-dtype", "--no-configs"]
+    if dump is not None:
+        cmd += ["--dump-outputs", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
-def test_bench_under_torchrun_with_a_real_rccl_group_matches_plain_run():
+def test_bench_under_torchrun_with_a_real_rccl_group_matches_plain_run(tmp_path):
     """`python -m torch.distributed.run --nproc-per-node 1 bench.py` builds a nccl (= RCCL) process group of one rank and, with
     PXA_DP_FORCE_COLLECTIVES=1, really all-reduces every gradient bucket from the engine's hooks while backward runs - the N > 1 code path,
     as far as one GPU can execute it.  The loss after two optimizer steps must equal the run without a process group up to the run-to-run
     noise of the fp32 atomics in the reductions (measured 1e-5 relative between two identical runs)."""
-    plain = _bench({}, [sys.executable])
+    plain = _bench({}, [sys.executable], dump=tmp_path / "plain")
     port = str(29500 + os.getpid() % 2000)
     pg = _bench({"PXA_DP_FORCE_COLLECTIVES": "1", "PXA_DP_TRACE": "1", "PXA_DP_TRACE_PRINT": "0"}, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                                                    "--master-addr", "127.0.0.1", "--master-port", port])
+                                                    "--master-addr", "127.0.0.1", "--master-port", port], dump=tmp_path / "pg")
     print("\nfinal_loss plain", plain["final_loss"], "rccl world-1", pg["final_loss"])
     assert pg["process_group"] == "nccl" and plain["process_group"] is None
     assert abs(pg["final_loss"] - plain["final_loss"]) < 1e-4 * abs(plain["final_loss"])
@@ -103,6 +105,15 @@ def test_bench_under_torchrun_with_a_real_rccl_group_matches_plain_run():
     assert names == ["final"] + [f"blocks.{i}" for i in reversed(range(28))] + ["cond"], names
     assert all(b["launched_from"] == "hook" for b in tr["buckets"]) and tr["exposed_ms"] >= 0.0 and tr["world"] == 1
     assert all(b["passed_ms"] >= b["ready_ms"] for b in tr["buckets"]) and "dp_trace" not in plain
+    # --dump-outputs: the last timed step's outputs, float32, the same on both paths up to the reductions' atomics (two identical 1024px runs of the
+    # fp16 build: gradient sample 7e-4 apart, loss 1.5e-6, weights 1.3e-6)
+    import numpy as np
+    names = ("loss", "mse", "vb", "grad_norm", "loss_scale", "params_sample", "grads_sample")
+    dp, dg = ({n: np.load(d / f"{n}.npy") for n in names} for d in (tmp_path / "plain", tmp_path / "pg"))
+    assert dp["loss"].shape == (4,) and dp["params_sample"].dtype == np.float32 and all(np.isfinite(v).all() for v in dp.values())
+    assert abs(float(dp["loss"].mean()) - plain["final_loss"]) < 1e-6 * abs(plain["final_loss"])
+    for n, tol in (("loss", 1e-4), ("params_sample", 1e-4), ("grads_sample", 5e-3)):
+        assert np.linalg.norm(dg[n] - dp[n]) <= tol * np.linalg.norm(dp[n]), (n, float(np.linalg.norm(dg[n] - dp[n]) / np.linalg.norm(dp[n])))
 
 
 def test_train_entry_point_fp16_accumulation_schedule(tmp_path):

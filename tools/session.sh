@@ -28,8 +28,8 @@ r_smoke() {
   timeout 900 python __graft_entry__.py smoke >> $O/${tag}_smoke.txt 2>&1; echo "smoke rc=$?" >> $O/${tag}_smoke.txt
   grep -v amdgpu $O/${tag}_smoke.txt | tail -n 12 | cut -c1-600
 }
-r_bench() {      # the default bench line with every leg (what the driver runs)
-  timeout 2400 python bench.py "$@" > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
+r_bench() {      # the bench line with every leg (--full)
+  timeout 2400 python bench.py --full "$@" > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
   cut -c1-1500 $O/${tag}_bench_default.json; tail -n 3 $O/${tag}_bench_default.err
 }
 r_profile_step() {   # rocprofv3 --kernel-trace --stats of the benchmark's training step -> per-kernel csv + family table
