@@ -1497,6 +1497,10 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
           __builtin_amdgcn_s_waitcnt(0xc07f);          // reads returned before the slice is overwritten
         }
       }
+      // PAIR with an odd m-tile count: the waves of the last pair's second half have mw >= M (see remcol above).  Their sums are all zero, but their
+      // atomics would still be issued - and for the statistics onto image index gn_B, i.e. for slot 15 past the end of gn_part.  They are skipped below;
+      // the column sums have no paired instance, so there the condition is a compile-time one.
+      static_assert(!(PAIR && (EPI == 2 || EPI == 3)), "column sums in a paired instance: guard their atomics with mw < p.M as the statistics are");
       if (want_cs) {                                   // lanes with the same chunk (lane % LPR) hold partial sums of the same 8 columns
 #pragma unroll
         for (int e = 0; e < 8; e++) {
@@ -1507,7 +1511,9 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
           if (lane < LPR && n < p.N) atomicAdd(p.colsum + (size_t)((mw >> 7) % PXA_COLSUM_SLOTS) * p.colsum_stride + n, v);
         }
       }
-      if (want_st) {
+      // mw < p.M (wave-uniform): a wave wholly beyond M has st_img == gn_B and nothing to add.  The counted wait of the next item stays true: prev_stores
+      // below counts these 4 atomics only for `interior` waves (mw + tm_eff * 32 <= p.M), a wave beyond M already reports 0 there.
+      if (want_st && mw < p.M) {
         float* dst = p.gn_part + ((size_t)((mw >> 7) % PXA_COLSUM_SLOTS) * p.gn_B + st_img) * (p.N / 4) * 2;
 #pragma unroll
         for (int h = 0; h < 2; h++) {                  // lanes with the same chunk hold partial sums of the same two quads
