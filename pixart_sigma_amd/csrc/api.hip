@@ -4,6 +4,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <utility>
 
 static thread_local char g_err[512] = "";
 
@@ -12,6 +15,19 @@ void pxa_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+hipError_t pxa::lds_optin(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, hipError_t> state;
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = state.find({dev, fn});
+  if (it != state.end()) return it->second;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) (void)hipGetLastError();      // reported through the return value: the next launch check must not find it
+  state[{dev, fn}] = e;
+  return e;
 }
 extern "C" const char* pxa_last_error(void) { return g_err; }
 extern "C" int pxa_abi_version(void) { return PXA_ABI_VERSION; }

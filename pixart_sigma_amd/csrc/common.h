@@ -209,6 +209,11 @@ __device__ __forceinline__ float half_wave_sum(float v) {  // reduce inside each
 }
 __device__ __forceinline__ float wave_sum(float v) { v = half_wave_sum(v); return v + __shfl_xor(v, 32); }
 
+// Opt a kernel in to `bytes` of dynamic LDS (more than the 64 KiB a launch gets unasked).  The opt-in is per device and per function, and launches come
+// from both the main and the autograd thread: tried once per (device, function) under a lock, every later call returns that attempt's result (api.hip).
+// What a failure means is the caller's business: the GEMM launchers return -3 with their message, the attention dispatch takes the streaming kernels.
+hipError_t lds_optin(const void* fn, int bytes);
+
 }  // namespace pxa
 
 // thread-local last-error string for the C ABI (api.hip)

@@ -1582,16 +1582,14 @@ int launch_pers(GemmParams p, int split, hipStream_t s) {
   static_assert(!SEG || LAYOUT == 0, "segmented A: layout NT");
   p.split = split;
   constexpr int LDSP = 4 * 40960;                      // the ring (4 x 40 KiB slots) = the CU's whole 160 KiB: one workgroup per CU
-  static bool attr_set_pp = false;
-  static int n_cu = 0;
-  if (!attr_set_pp) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSP);
-    if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_pers<%d,%d>): %s", LAYOUT, EPI, hipGetErrorString(e)); return -3; }
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), LDSP);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_pers<%d,%d>): %s", LAYOUT, EPI, hipGetErrorString(e)); return -3; }
+  static int n_cu = 0;                                 // (one kind of device per process)
+  if (!n_cu) {
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { pxa_set_error("gemm_pers: device query failed"); return -3; }
     n_cu = prop.multiProcessorCount;
-    attr_set_pp = true;
   }
   const int tiles = pers_tiles(p.M, p.N, RM) * split;
   p.sched_slot = dynamic_items() ? (int)(g_launch_seq.fetch_add(1u) & 63u) : -1;
@@ -1605,12 +1603,8 @@ int launch_glds_e(GemmParams p, int split, hipStream_t s) {
   p.split = split;
   constexpr int LDSG = 2 * (TBM + TBN) * 128;
   static_assert(WM * WN * (TBM / WM) * EPI_STRIDE <= LDSG, "staged epilogue must fit the operand stages");
-  static bool attr_set_g = false;
-  if (!attr_set_g) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSG);
-    if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_glds<%d,%d,%d>): %s", LAYOUT, TBM, TBN, hipGetErrorString(e)); return -3; }
-    attr_set_g = true;
-  }
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), LDSG);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_glds<%d,%d,%d>): %s", LAYOUT, TBM, TBN, hipGetErrorString(e)); return -3; }
   dim3 grid(((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN) * split, 1, 1);
   hipLaunchKernelGGL((gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), grid, dim3(WM * WN * 64), LDSG, s, p);
   PXA_LAUNCH_CHECK();
@@ -1654,12 +1648,8 @@ int launch(GemmParams p, int split, hipStream_t s) {
   p.split = split;
   constexpr bool A_KC = (LAYOUT != 2), B_KC = (LAYOUT == 0);
   constexpr int LDS = 2 * ((A_KC ? KC_BYTES : RC_BYTES) + (B_KC ? KC_BYTES : RC_BYTES));
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm<%d>, %d): %s", LAYOUT, LDS, hipGetErrorString(e)); return -3; }
-    attr_set = true;
-  }
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_kernel<LAYOUT>), LDS);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm<%d>, %d): %s", LAYOUT, LDS, hipGetErrorString(e)); return -3; }
   dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * split, 1, 1);
   const bool fast = (p.K % BK == 0) && (p.k_per_split % BK == 0) && !getenv("PXA_GEMM_NO_GLDS");
   if (p.k_seg) {                                          // implicit 3x3 convolution (checked by pxa_gemm: NT, K and k_seg multiples of 64)

@@ -3,7 +3,7 @@
 * the one-wave-per-SIMD forward kernel keeps its promises: no scratch, no v_accvgpr traffic on the tile loop's hot path (the compiler's own split of a
   512-register kernel cost 177 spills and ~440 moves per tile before the accumulator half was pinned through asm constraints), one barrier per tile;
 * M0 (the LDS-DMA destination, written inside common.h lds_dma16 / attn.hip dma_pair without a clobber the compiler would honour) has no other user
-  in any kernel of attn.hip / gemm.hip (a compiler-generated M0 use between the statements would be corrupted silently)."""
+  in any kernel of attn.hip (with attn_ab.h, which it includes) / gemm.hip (a compiler-generated M0 use between the statements would be corrupted silently)."""
 import os
 import re
 import subprocess
