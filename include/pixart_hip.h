@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define PXA_ABI_VERSION 9
+#define PXA_ABI_VERSION 10
 /* Kernels that fuse a bias-gradient column sum add into one of PXA_COLSUM_SLOTS partial rows ([slot][stride] fp32, caller-zeroed),
  * chosen per sample / row tile, so no address sees thousands of atomics; pxa_colsum_reduce folds the partials into the gradient. */
 #define PXA_COLSUM_SLOTS 16
@@ -98,13 +98,19 @@ typedef struct {
 /* Upper bound of the split-K workspace (in floats) pxa_gemm may use for an (M, N) fp32-accumulate output. */
 long pxa_gemm_splitk_ws_elems(int M, int N);
 int pxa_gemm(const pxa_gemm_args* args, hipStream_t stream);
+/* (ABI 10) What pxa_gemm would do with `args`, as one line of text in `out` - the kernel instance as its template is written, then
+ * "split= k_per_split= accumulate= try_nt4= colsum_pass_after= splitk_reduce=" - through the same checks and the same choice, without touching a device
+ * (no GPU needed; pointers are only compared with NULL).  A call pxa_gemm refuses is refused here with the same return code and pxa_last_error().
+ * try_nt4=1: pxa_gemm first offers the call to the one-wave-per-SIMD NT kernel (PXA_GEMM_NT4, off by default); the instance named runs when that declines. */
+int pxa_gemm_plan(const pxa_gemm_args* args, char* out, int out_len);
 /* How the persistent 256 x 256 kernels of the token GEMMs (NT / NN, 16-bit output) hand their items to the workgroups:
  *   0 (default)  static split - workgroup b takes items b, b + #CUs, ... : the fastest when the GEMM owns the GPU (training step on one GPU: -4.7 ms of 434,
  *                profiles/r4_38_step_ab_gemm_sched.txt);
  *   1            dynamic per-XCD cursors - a workgroup that starts late (a collective of the data-parallel all-reduce holds its CU: the reference overlaps
  *                DDP's bucket all-reduce with the backward, train_scripts/train.py:128-133 through accelerate) leaves its items to the others instead of
  *                doubling the kernel's time (profiles/r03*_contention*).  The data-parallel runtime (pixart_sigma_amd/dp.py) switches it on for world size > 1.
- * Process-wide; returns the previous setting.  Environment overrides for A/B runs: PXA_GEMM_STATIC=1 / PXA_GEMM_DYNAMIC=1 (read at the first GEMM). */
+ * Process-wide; returns the previous setting.  Environment overrides for A/B runs: PXA_GEMM_STATIC=1 / PXA_GEMM_DYNAMIC=1 (read at the first persistent GEMM and by every call of this function;
+ * the other PXA_GEMM_* switches: GemmKnobs in csrc/gemm.hip). */
 int pxa_gemm_set_dynamic_items(int on);
 
 /* ---------------------------------------------------------------------------------------------- adaLN-single rows

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "gemm_params.h"
 #include "../../include/pixart_hip.h"
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -1555,160 +1556,59 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
     for (int k = 0; k < 9; k++) sched[k] = 0u;         // last workgroup out: the slot is clean for a later launch
 }
 
-// item hand-out of the persistent NT / NN kernels: pxa_gemm_set_dynamic_items (include/pixart_hip.h); -1 = not set yet -> the environment, else static
-static std::atomic<int> g_dynamic_items{-1};
-static inline bool dynamic_items() {
-  int v = g_dynamic_items.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = getenv("PXA_GEMM_DYNAMIC") != nullptr && getenv("PXA_GEMM_STATIC") == nullptr ? 1 : 0;
-    int expect = -1;
-    g_dynamic_items.compare_exchange_strong(expect, v);
-    v = g_dynamic_items.load(std::memory_order_relaxed);
-  }
-  return v != 0;
+// The environment switches of the dispatch (A/B runs, tests): read here and nowhere else, PXA_GEMM_NO_GLDS on every call, the others once per process (at the
+// first pxa_gemm / pxa_gemm_plan).  PXA_GEMM_NT4 belongs to gemm_nt4.hip and is read there, per call.
+struct GemmKnobs { bool no_staged, no_pers, no_half, seg_half; int tile; bool ascending, no_glds; };
+GemmKnobs read_gemm_knobs() {
+  static const bool no_staged = getenv("PXA_GEMM_NO_STAGED_EPILOGUE") != nullptr;   // bf16-only outputs of gemm_glds_kernel take the direct epilogue
+  static const bool no_pers = getenv("PXA_GEMM_NO_PERSISTENT") != nullptr;          // never gemm_pers_kernel
+  static const bool no_half = getenv("PXA_GEMM_NO_HALF_ITEMS") != nullptr;          // token GEMMs pad the remainder column to a full tile
+  static const bool seg_half = getenv("PXA_GEMM_SEG_HALF") != nullptr;              // implicit convolutions: HALF remainder items (round 5) instead of PAIRED
+  static const int tile = [] { const char* f = getenv("PXA_GEMM_TILE"); return f ? atoi(f) * (strstr(f, "x128") ? -1 : 1) : 0; }();   // "128" | "256x128" (-256) | "256"
+  static const bool ascending = getenv("PXA_GEMM_ASCENDING") != nullptr;            // ignore items_descending
+  return GemmKnobs{no_staged, no_pers, no_half, seg_half, tile, ascending, getenv("PXA_GEMM_NO_GLDS") != nullptr};   // NO_GLDS: plain GEMMs on gemm_kernel
 }
-static std::atomic<unsigned> g_launch_seq{0};          // cursor-slot round robin, shared by every instantiation of the persistent kernel
+// item hand-out of the persistent NT / NN kernels: pxa_gemm_set_dynamic_items (include/pixart_hip.h); -1 = not set yet -> the environment, else static.
+// PXA_GEMM_STATIC / PXA_GEMM_DYNAMIC (A/B override; -1 = neither): read by the first persistent launch and by every pxa_gemm_set_dynamic_items
+int dynamic_items_env() { return getenv("PXA_GEMM_STATIC") ? 0 : getenv("PXA_GEMM_DYNAMIC") ? 1 : -1; }
+std::atomic<int> g_dynamic_items{-1}; std::atomic<unsigned> g_launch_seq{0};                 // cursor-slot round robin, shared by every instantiation of the persistent kernel
+bool dynamic_items() {
+  int expect = -1;
+  if (g_dynamic_items.load(std::memory_order_relaxed) < 0) g_dynamic_items.compare_exchange_strong(expect, dynamic_items_env() == 1 ? 1 : 0);
+  return g_dynamic_items.load(std::memory_order_relaxed) != 0;
+}
+bool pers_halfcol(int N) { return N % 256 > 0 && N % 256 <= 128; }      // the 128-wide remainder column of the persistent kernel's 256 x 256 tiling
 // work items of the persistent kernel per k-slice (must match the kernel's own count)
-static inline bool pers_pairing(int M, int N) { (void)M; return N % 256 > 0 && N % 256 <= 128; }
-static inline bool pers_halfcol(int N) { return N % 256 > 0 && N % 256 <= 128; }
-static inline int pers_tiles(int M, int N, int rm) {
+int pers_tiles(int M, int N, int rm) {
   const int mt = (M + 255) / 256, ntf = N / 256;
   if (rm == 2 && pers_halfcol(N)) return mt * ntf + mt;
-  const bool pairing = rm == 1 && pers_pairing(M, N);
+  const bool pairing = rm == 1 && pers_halfcol(N);
   return mt * (pairing ? ntf : (N + 255) / 256) + (pairing ? (mt + 1) / 2 : 0);
 }
-template <int LAYOUT, int EPI, int RM = 0, bool SEG = false>
-int launch_pers(GemmParams p, int split, hipStream_t s) {
-  static_assert(!SEG || LAYOUT == 0, "segmented A: layout NT");
-  p.split = split;
-  constexpr int LDSP = 4 * 40960;                      // the ring (4 x 40 KiB slots) = the CU's whole 160 KiB: one workgroup per CU
-  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), LDSP);
-  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_pers<%d,%d>): %s", LAYOUT, EPI, hipGetErrorString(e)); return -3; }
-  static int n_cu = 0;                                 // (one kind of device per process)
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { pxa_set_error("gemm_pers: device query failed"); return -3; }
-    n_cu = prop.multiProcessorCount;
-  }
-  const int tiles = pers_tiles(p.M, p.N, RM) * split;
-  p.sched_slot = dynamic_items() ? (int)(g_launch_seq.fetch_add(1u) & 63u) : -1;
-  hipLaunchKernelGGL((gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), LDSP, s, p);
-  PXA_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int LAYOUT, int TBM, int TBN, int WM, int WN, int EPI, bool SEG = false>
-int launch_glds_e(GemmParams p, int split, hipStream_t s) {
-  p.split = split;
-  constexpr int LDSG = 2 * (TBM + TBN) * 128;
-  static_assert(WM * WN * (TBM / WM) * EPI_STRIDE <= LDSG, "staged epilogue must fit the operand stages");
-  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), LDSG);
-  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_glds<%d,%d,%d>): %s", LAYOUT, TBM, TBN, hipGetErrorString(e)); return -3; }
-  dim3 grid(((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN) * split, 1, 1);
-  hipLaunchKernelGGL((gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), grid, dim3(WM * WN * 64), LDSG, s, p);
-  PXA_LAUNCH_CHECK();
-  return 0;
-}
-template <int LAYOUT, int TBM, int TBN, int WM, int WN>
-int launch_glds(GemmParams p, int split, hipStream_t s) {
-  // bf16-only outputs of the forward / dX GEMMs take the LDS-staged, fully coalesced epilogue (separate kernel instances, so
-  // neither epilogue's registers burden the other)
-  static const bool no_stage = getenv("PXA_GEMM_NO_STAGED_EPILOGUE") != nullptr;
-  const bool dual = (p.act == 1 && p.out2 != nullptr) || p.act == 3;   // two outputs: the direct epilogue
-  static const bool no_pers = getenv("PXA_GEMM_NO_PERSISTENT") != nullptr;
-  if (LAYOUT != 2 && TBM == 256 && TBN == 256 && split == 1 && p.out && !p.outf && !no_pers) {
-    constexpr int LY = LAYOUT == 2 ? 0 : LAYOUT;
-    static const bool no_half = getenv("PXA_GEMM_NO_HALF_ITEMS") != nullptr;   // A/B: pad the remainder column to a full tile
-    const bool hc = pers_halfcol(p.N) && !no_half;
-    if constexpr (LAYOUT == 0) {                          // the one-wave-per-SIMD NT kernel (gemm_nt4.hip) where it applies
-      if (p.act == 0 && !p.colsum) { GemmParams q = p; q.split = 1; const int rc = pxa_gemm_nt4_launch(q, s); if (rc <= 0) return rc; }
+// Split-K weight-gradient GEMMs (K = tokens, 65536): a handful of long-running workgroups, so wave quantisation against the
+// 256 CUs decides the time.  Pick (tile, split) minimising  rounds x k-tiles x tile cost  + atomic epilogue traffic.
+// Candidates: 128 x 128 tiles, two workgroups per CU (512 slots, ~760 TF/s when full) and the persistent 256 x 256 kernel
+// (256 slots, ~1050 TF/s when full since the 16-MFMA phases; with the round-1 constants 800 / 1000 the 1152 x 1152 gradients still went
+// to the 128 kernel: 232-245 us against 212 for 25 padded 256 tiles x 10 k-slices).
+// time = rounds x k-range x tile FLOPs / per-slot rate  +  slab write + read + reduce.
+void cost_model(int M, int N, int K, int& split, int& tile) {
+  struct Cfg { int tile, bm, bn, slots; double rate; };
+  const Cfg cfgs[2] = {{128, 128, 128, 512, 760e12}, {256, 256, 256, 256, 1050e12}};
+  double best = 1e30;
+  for (const Cfg& c : cfgs) {
+    if (c.tile == 256 && (M < 256 || N < 256)) continue;
+    const long tiles = c.tile == 256 ? pers_tiles(M, N, 1) : (long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
+    for (int sp = 1; sp <= 16; sp++) {
+      const int kp = ((K + sp - 1) / sp + BK - 1) / BK * BK;
+      if ((long)kp * (sp - 1) >= K) continue;               // would leave an empty split
+      const long rounds = (tiles * sp + c.slots - 1) / c.slots;
+      const double t = rounds * (double)kp * c.bm * c.bn * 2.0 / (c.rate / c.slots) + (sp > 1 ? 2.0 * sp * M * N * 4.0 / 3.5e12 + 4e-6 : 0.0);
+      if (t < best) { best = t; split = sp; tile = c.tile; }
     }
-    if (p.act == 0 && !p.colsum) return hc ? launch_pers<LY, 0, 2>(p, 1, s) : launch_pers<LY, 0, 0>(p, 1, s);
-    if (p.act == 3 && !p.colsum) return launch_pers<LY, 1, 0>(p, 1, s);      // fc1 forward: N = 4608, no remainder column
-    if (p.act == 4 && p.colsum) return hc ? launch_pers<LY, 2, 2>(p, 1, s) : launch_pers<LY, 2, 0>(p, 1, s);
-    if constexpr (LY == 0) { if (p.act == 1 && !p.out2 && !p.colsum && !hc) return launch_pers<0, 7, 0>(p, 1, s); }
-    return launch_pers<LY, 3, 0>(p, 1, s);
   }
-  // fp32 weight gradients (TN, split-K slabs / single-slice read-modify-write / plain store): the same persistent kernel
-  if (LAYOUT == 2 && TBM == 256 && TBN == 256 && p.outf && !p.out && !p.bias && p.act == 0 && p.accumulate != 1 && !p.colsum && !no_pers)
-    return pers_pairing(p.M, p.N) ? launch_pers<2, 0, 1>(p, split, s) : launch_pers<2, 0, 0>(p, split, s);
-  if (LAYOUT != 2 && p.out && !p.outf && !dual && !no_stage) return launch_glds_e<LAYOUT, TBM, TBN, WM, WN, 1>(p, split, s);
-  if (p.colsum) {                                         // not fused on this path: separate column-sum pass over the output
-    float* cs = p.colsum;
-    p.colsum = nullptr;
-    int rc = launch_glds_e<LAYOUT, TBM, TBN, WM, WN, 0>(p, split, s);
-    return rc ? rc : pxa_colsum_bf16(p.out, p.ldo, cs, p.M, p.N, s);
-  }
-  return launch_glds_e<LAYOUT, TBM, TBN, WM, WN, 0>(p, split, s);
 }
-
-template <int LAYOUT>
-int launch(GemmParams p, int split, hipStream_t s) {
-  p.split = split;
-  constexpr bool A_KC = (LAYOUT != 2), B_KC = (LAYOUT == 0);
-  constexpr int LDS = 2 * ((A_KC ? KC_BYTES : RC_BYTES) + (B_KC ? KC_BYTES : RC_BYTES));
-  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_kernel<LAYOUT>), LDS);
-  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm<%d>, %d): %s", LAYOUT, LDS, hipGetErrorString(e)); return -3; }
-  dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * split, 1, 1);
-  const bool fast = (p.K % BK == 0) && (p.k_per_split % BK == 0) && !getenv("PXA_GEMM_NO_GLDS");
-  if (p.k_seg) {                                          // implicit 3x3 convolution (checked by pxa_gemm: NT, K and k_seg multiples of 64)
-    if constexpr (LAYOUT == 0) {
-      static const bool no_pers_seg = getenv("PXA_GEMM_NO_PERSISTENT") != nullptr;
-      if (p.out && !p.outf && (p.act == 0 || p.act == 5) && p.M >= 1024 && p.N >= 128 && p.N % 128 == 0 && p.k_seg % 32 == 0 && !no_pers_seg) {
-        // Remainder columns of 128 (the VAE's 128-channel layers: N = 128 is ONLY a remainder column).  Round 6: PAIRED items - the remainder columns of two
-        // consecutive m-tiles as one 512 x 128 item on full 128 x 64 wave tiles - instead of HALF items (256 x 128 on 64 x 64 wave tiles: half the MFMAs per
-        // barrier pair, 500-640 TFLOP/s on the 512 x 512 x 128-channel layers of the decoder, profiles/r6_01_vae_layer_table.txt).  The token GEMMs keep HALF
-        // items: there the remainder column is a ninth of the work and equal rounds matter more (see RM above).  PXA_GEMM_SEG_HALF=1: the round-5 choice (A/B).
-        static const bool seg_half = getenv("PXA_GEMM_SEG_HALF") != nullptr;
-        const bool hc = pers_halfcol(p.N), pair = hc && !seg_half && p.M >= 512;
-        if (p.gn_part) {                                 // + GroupNorm statistics of the output
-          if (p.act == 5) return pair ? launch_pers<0, 6, 1, true>(p, 1, s) : hc ? launch_pers<0, 6, 2, true>(p, 1, s) : launch_pers<0, 6, 0, true>(p, 1, s);
-          return pair ? launch_pers<0, 5, 1, true>(p, 1, s) : hc ? launch_pers<0, 5, 2, true>(p, 1, s) : launch_pers<0, 5, 0, true>(p, 1, s);
-        }
-        if (p.act == 5) return pair ? launch_pers<0, 4, 1, true>(p, 1, s) : hc ? launch_pers<0, 4, 2, true>(p, 1, s) : launch_pers<0, 4, 0, true>(p, 1, s);   // conv + residual
-        return pair ? launch_pers<0, 0, 1, true>(p, 1, s) : hc ? launch_pers<0, 0, 2, true>(p, 1, s) : launch_pers<0, 0, 0, true>(p, 1, s);
-      }
-      if (p.gn_part) { pxa_set_error("pxa_gemm: gn_part needs the persistent implicit-convolution path (bf16 output, M >= 1024, N a multiple of 128)"); return -1; }
-      if (p.out && !p.outf && p.act == 0) return launch_glds_e<0, 128, 128, 2, 2, 1, true>(p, 1, s);
-      return launch_glds_e<0, 128, 128, 2, 2, 0, true>(p, 1, s);
-    }
-    return -2;
-  }
-  if (fast) {
-    static const char* force = getenv("PXA_GEMM_TILE");   // "128" | "256x128" | "256" : A/B experiments
-    int tile = force ? atoi(force) * (strstr(force, "x128") ? -1 : 1) : 0;
-    if (!tile) tile = p.tile_hint;
-    if (!tile) tile = (p.M >= 1024 && p.N >= 1024) ? 256 : 128;
-    if (tile == 128) return launch_glds<LAYOUT, 128, 128, 2, 2>(p, split, s);
-    if (tile == -256) return launch_glds<LAYOUT, 256, 128, 4, 2>(p, split, s);
-    return launch_glds<LAYOUT, 256, 256, 2, 4>(p, split, s);
-  }
-  float* cs_fallback = p.colsum;
-  p.colsum = nullptr;
-  hipLaunchKernelGGL(gemm_kernel<LAYOUT>, grid, dim3(256), LDS, s, p);
-  PXA_LAUNCH_CHECK();
-  if (cs_fallback) return pxa_colsum_bf16(p.out, p.ldo, cs_fallback, p.M, p.N, s);
-  return 0;
-}
-}  // namespace
-
-namespace {
-// out[m][n] += sum_z slab[z][m][n]   (split-K combine at the launch boundary: plain 16-byte loads/stores, no atomics)
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int ld, int M, int N, int split) {
-  const long i4 = blockIdx.x * 256L + threadIdx.x, n4 = N / 4;
-  if (i4 >= (long)M * n4) return;
-  const int m = i4 / n4, n = (i4 - (long)m * n4) * 4;
-  float4 s = *reinterpret_cast<const float4*>(out + (size_t)m * ld + n);
-  for (int z = 0; z < split; z++) {
-    const float4 v = *reinterpret_cast<const float4*>(slab + ((size_t)z * M + m) * N + n);
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  *reinterpret_cast<float4*>(out + (size_t)m * ld + n) = s;
-}
-}  // namespace
-
-extern "C" int pxa_gemm(const pxa_gemm_args* a, hipStream_t stream) {
+// checks of the argument block, the kernel's parameter block (p.split = the k-slices that are not empty) and the cost model's tile (0 = no opinion)
+int fill_gemm(const pxa_gemm_args* a, const GemmKnobs& k, GemmParams& p, int& tile) {
   PXA_CHECK(a && a->A && a->B, "pxa_gemm: null operand");
   PXA_CHECK(a->layout >= 0 && a->layout <= 2, "pxa_gemm: bad layout %d", a->layout);
   PXA_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "pxa_gemm: bad shape %d %d %d", a->M, a->N, a->K);
@@ -1725,54 +1625,21 @@ extern "C" int pxa_gemm(const pxa_gemm_args* a, hipStream_t stream) {
   if (a->colsum) PXA_CHECK(a->out_bf16 && !a->out_f32, "pxa_gemm: colsum needs a bf16 output");
   int split = a->split_k < 1 ? 1 : a->split_k;   // 0 = choose here (only for fp32 atomic-accumulate outputs)
   if (split > 1) PXA_CHECK(a->out_f32 && a->accumulate && !a->out_bf16 && a->act == 0 && !a->bias, "pxa_gemm: split_k>1 needs fp32 atomic accumulate output only");
-  GemmParams p;
-  p.A = (const bf16_t*)a->A; p.B = (const bf16_t*)a->B; p.lda = a->lda; p.ldb = a->ldb;
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.bias = a->bias; p.aux = (const bf16_t*)a->aux; p.ldaux = a->ldaux;
-  p.out = (bf16_t*)a->out_bf16; p.out2 = (bf16_t*)a->out2_bf16; p.ldo = a->ld_out;
-  p.outf = a->out_f32; p.ldf = a->ld_f32;
-  p.act = a->act; p.accumulate = a->accumulate;
-  p.tile_hint = 0;
-  static const bool force_asc = getenv("PXA_GEMM_ASCENDING") != nullptr;      // A/B: ignore items_descending
-  p.desc = (a->items_descending && !force_asc) ? 1 : 0;
-  p.k_seg = a->k_seg; p.seg_jump = a->k_seg ? a->a_seg_stride - a->k_seg : 0;
-  p.k_tap = a->k_seg ? a->k_tap : 0; p.tap_s = a->a_seg_stride;
-  if (a->k_seg && a->k_tap)
-    PXA_CHECK(a->k_tap % BK == 0 && a->k_seg == 3 * a->k_tap && a->K == 3 * a->k_seg, "pxa_gemm: k_tap=%d needs k_seg = 3 k_tap, K = 9 k_tap, k_tap a multiple of %d", a->k_tap, BK);
+  p.A = (const bf16_t*)a->A; p.B = (const bf16_t*)a->B; p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
+  p.bias = a->bias; p.aux = (const bf16_t*)a->aux; p.ldaux = a->ldaux; p.out = (bf16_t*)a->out_bf16; p.out2 = (bf16_t*)a->out2_bf16; p.ldo = a->ld_out;
+  p.outf = a->out_f32; p.ldf = a->ld_f32; p.act = a->act; p.accumulate = a->accumulate; tile = 0;
+  p.desc = (a->items_descending && !k.ascending) ? 1 : 0;
+  p.k_seg = a->k_seg; p.seg_jump = a->k_seg ? a->a_seg_stride - a->k_seg : 0; p.k_tap = a->k_seg ? a->k_tap : 0; p.tap_s = a->a_seg_stride;
+  if (a->k_seg && a->k_tap) PXA_CHECK(a->k_tap % BK == 0 && a->k_seg == 3 * a->k_tap && a->K == 3 * a->k_seg, "pxa_gemm: k_tap=%d needs k_seg = 3 k_tap, K = 9 k_tap, k_tap a multiple of %d", a->k_tap, BK);
   if (a->k_seg) {
     PXA_CHECK(a->layout == 0 && split == 1 && !a->colsum, "pxa_gemm: k_seg needs layout NT, no split-K, no colsum");
     PXA_CHECK(a->k_seg > 0 && a->k_seg % BK == 0 && a->K % a->k_seg == 0 && a->a_seg_stride % 8 == 0, "pxa_gemm: k_seg=%d must be a multiple of %d dividing K=%d (segment stride a multiple of 8)", a->k_seg, BK, a->K);
   }
-  if (a->split_k == 0 && a->out_f32 && a->accumulate && !a->out_bf16 && a->act == 0 && !a->bias && a->K % BK == 0) {
-    // Split-K weight-gradient GEMMs (K = tokens, 65536): a handful of long-running workgroups, so wave quantisation against the
-    // 256 CUs decides the time.  Pick (tile, split) minimising  rounds x k-tiles x tile cost  + atomic epilogue traffic.
-    // Candidates: 128 x 128 tiles, two workgroups per CU (512 slots, ~760 TF/s when full) and the persistent 256 x 256 kernel
-    // (256 slots, ~1050 TF/s when full since the 16-MFMA phases; with the round-1 constants 800 / 1000 the 1152 x 1152 gradients still went
-    // to the 128 kernel: 232-245 us against 212 for 25 padded 256 tiles x 10 k-slices).
-    // time = rounds x k-range x tile FLOPs / per-slot rate  +  slab write + read + reduce.
-    struct Cfg { int tile, bm, bn, slots; double rate; };
-    const Cfg cfgs[2] = {{128, 128, 128, 512, 760e12}, {256, 256, 256, 256, 1050e12}};
-    double best = 1e30;
-    for (const Cfg& c : cfgs) {
-      if (c.tile == 256 && (a->M < 256 || a->N < 256)) continue;
-      const long tiles = c.tile == 256 ? pers_tiles(a->M, a->N, 1) : (long)((a->M + c.bm - 1) / c.bm) * ((a->N + c.bn - 1) / c.bn);
-      for (int sp = 1; sp <= 16; sp++) {
-        const int kp = ((a->K + sp - 1) / sp + BK - 1) / BK * BK;
-        if ((long)kp * (sp - 1) >= a->K) continue;               // would leave an empty split
-        const long rounds = (tiles * sp + c.slots - 1) / c.slots;
-        const double t = rounds * (double)kp * c.bm * c.bn * 2.0 / (c.rate / c.slots) + (sp > 1 ? 2.0 * sp * a->M * a->N * 4.0 / 3.5e12 + 4e-6 : 0.0);
-        if (t < best) { best = t; split = sp; p.tile_hint = c.tile; }
-      }
-    }
-  }
-  int kps = ((a->K + split - 1) / split + BK - 1) / BK * BK;
-  p.k_per_split = kps;
-  split = (a->K + kps - 1) / kps;
-  p.slab = nullptr;
-  p.colsum = a->colsum; p.colsum_stride = a->colsum_stride;
-  p.gn_part = a->gn_part; p.gn_img_rows = a->gn_img_rows; p.gn_rp = a->gn_row_pitch; p.gn_h = a->gn_h; p.gn_w = a->gn_w;
-  p.gn_B = 0; p.gn_inv_rp = 0.f;
-  p.up_rp = 0; p.up_ip = 0; p.up_off = 0;
+  if (a->split_k == 0 && a->out_f32 && a->accumulate && !a->out_bf16 && a->act == 0 && !a->bias && a->K % BK == 0) cost_model(a->M, a->N, a->K, split, tile);
+  p.k_per_split = ((a->K + split - 1) / split + BK - 1) / BK * BK;
+  split = p.split = (a->K + p.k_per_split - 1) / p.k_per_split; p.tile_hint = tile; p.sched_slot = -1; p.slab = nullptr;    // (tile_hint: a kernel argument still)
+  p.colsum = a->colsum; p.colsum_stride = a->colsum_stride; p.gn_part = a->gn_part; p.gn_img_rows = a->gn_img_rows; p.gn_rp = a->gn_row_pitch; p.gn_h = a->gn_h; p.gn_w = a->gn_w;
+  p.gn_B = 0; p.gn_inv_rp = 0.f; p.up_rp = 0; p.up_ip = 0; p.up_off = 0;
   if (a->up_row_pitch) {
     PXA_CHECK(a->gn_part && a->k_seg && a->act == 0 && !a->k_tap, "pxa_gemm: up_row_pitch needs an implicit convolution with gn_part, act 0 and the plain segment order");
     PXA_CHECK(a->K == 2 * a->k_seg && a->up_row_pitch == 2 * a->gn_w + 2 && a->up_img_rows >= (2 * a->gn_h + 2) * a->up_row_pitch && (a->up_dy | 1) == 1 && (a->up_dx | 1) == 1,
@@ -1787,29 +1654,182 @@ extern "C" int pxa_gemm(const pxa_gemm_args* a, hipStream_t stream) {
               "pxa_gemm: bad padded-grid geometry for gn_part (h=%d w=%d row_pitch=%d img_rows=%d)", a->gn_h, a->gn_w, a->gn_row_pitch, a->gn_img_rows);
     p.gn_B = a->M / a->gn_img_rows; p.gn_inv_rp = 1.0f / (float)a->gn_row_pitch;
   }
-  if (p.accumulate && p.outf) {
+  if (p.accumulate && p.outf) {                                // fp32 accumulate: 1 = atomics, 2 = one slice reads and writes, 3 = slabs + splitk_reduce_kernel
     if (split == 1) p.accumulate = 2;
     else if (a->splitk_ws && a->splitk_ws_elems >= (long)split * a->M * a->N) { p.accumulate = 3; p.slab = a->splitk_ws; }
   }
-  int rc;
-  switch (a->layout) {
-    case 0: rc = launch<0>(p, split, stream); break;
-    case 1: rc = launch<1>(p, split, stream); break;
-    default: rc = launch<2>(p, split, stream); break;
+  return 0;
+}
+enum class GemmFamily { simple, glds, pers };                  // gemm_kernel, gemm_glds_kernel, gemm_pers_kernel
+// gemm_glds_kernel's EPI: staged = through LDS, fully coalesced, bf16 output only (+ fused column sums).  gemm_pers_kernel's EPI (the kernel derives its activation from it): act 0 | act 3, two outputs | act 4 + column sums | act, out2 and colsum read from the
+// params | act 5 (conv + residual) | act 0 + GroupNorm statistics of the output | act 5 + statistics | act 1, one output
+enum GldsEpi { GLDS_DIRECT = 0, GLDS_STAGED = 1 };
+enum PersEpi { PERS_PLAIN = 0, PERS_GELU_SAVE_GRAD = 1, PERS_MUL_AUX_COLSUM = 2, PERS_GENERIC = 3, PERS_ADD_AUX = 4, PERS_STATS = 5, PERS_ADD_AUX_STATS = 6, PERS_GELU = 7 };
+struct GemmPlan {
+  GemmFamily family; int layout, tile, epi, rm;   // glds: tile 0 = 128 x 128 (2 x 2 waves), 1 = 256 x 128 (4 x 2), 2 = 256 x 256 (2 x 4); GldsEpi / PersEpi; pers: rm =
+  bool seg; int split;     //  the remainder column as 0 = a padded full tile, 1 = PAIRED items, 2 = HALF items.  seg: segmented-K A; split: k-slices of the launch
+  bool try_nt4;            // pxa_gemm_nt4_launch first; the kernel named here runs when that answers "not mine"
+  bool colsum_pass_after;  // column sums not fused on this path: launch without them, then pxa_colsum_bf16 over the output
+};
+// Every eligibility rule and fallback of the dispatch.  No HIP call, no environment, no dereference.
+int choose_gemm(const GemmParams& p, int layout, int split, int tile_hint, const GemmKnobs& k, GemmPlan& g) {
+  g = GemmPlan{GemmFamily::simple, layout, 0, 0, 0, p.k_seg != 0, p.k_seg ? 1 : split, false, false};       // (the segmented kernels launch one slice)
+  const bool bf16_only = p.out && !p.outf, hc = pers_halfcol(p.N);
+  if (p.k_seg) {                                          // implicit 3x3 convolution (checked by fill_gemm: NT, K and k_seg multiples of 64)
+    if (layout != 0) return -2;
+    if (bf16_only && (p.act == 0 || p.act == 5) && p.M >= 1024 && p.N >= 128 && p.N % 128 == 0 && p.k_seg % 32 == 0 && !k.no_pers) {
+      // Remainder columns of 128 (the VAE's 128-channel layers: N = 128 is ONLY a remainder column).  Round 6: PAIRED items - the remainder columns of two
+      // consecutive m-tiles as one 512 x 128 item on full 128 x 64 wave tiles - instead of HALF items (256 x 128 on 64 x 64 wave tiles: half the MFMAs per
+      // barrier pair, 500-640 TFLOP/s on the 512 x 512 x 128-channel layers of the decoder, profiles/r6_01_vae_layer_table.txt).  The token GEMMs keep HALF
+      // items: there the remainder column is a ninth of the work and equal rounds matter more (see RM above).  PXA_GEMM_SEG_HALF=1: the round-5 choice (A/B).
+      const bool pair = hc && !k.seg_half && p.M >= 512;
+      g.family = GemmFamily::pers; g.rm = pair ? 1 : hc ? 2 : 0;
+      g.epi = p.gn_part ? (p.act == 5 ? PERS_ADD_AUX_STATS : PERS_STATS) : (p.act == 5 ? PERS_ADD_AUX : PERS_PLAIN);
+      return 0;
+    }
+    if (p.gn_part) { pxa_set_error("pxa_gemm: gn_part needs the persistent implicit-convolution path (bf16 output, M >= 1024, N a multiple of 128)"); return -1; }
+    g.family = GemmFamily::glds; g.epi = bf16_only && p.act == 0 ? GLDS_STAGED : GLDS_DIRECT;
+    return 0;
   }
+  if (p.K % BK != 0 || p.k_per_split % BK != 0 || k.no_glds) { g.colsum_pass_after = p.colsum != nullptr; return 0; }   // the slow path: gemm_kernel, column sums apart
+  const int want = k.tile ? k.tile : tile_hint ? tile_hint : (p.M >= 1024 && p.N >= 1024) ? 256 : 128, tile = want == 128 ? 0 : want == -256 ? 1 : 2;
+  const bool pers_ok = tile == 2 && !k.no_pers;
+  if (layout != 2 && pers_ok && split == 1 && bf16_only) {    // token GEMMs (forward / dX): the persistent 256 x 256 kernel
+    const bool half = hc && !k.no_half;                        // (A/B: pad the remainder column to a full tile)
+    g.family = GemmFamily::pers; g.try_nt4 = layout == 0 && p.act == 0 && !p.colsum;        // the one-wave-per-SIMD NT kernel (gemm_nt4.hip) where it applies
+    if (p.act == 0 && !p.colsum) { g.epi = PERS_PLAIN; g.rm = half ? 2 : 0; }
+    else if (p.act == 3 && !p.colsum) g.epi = PERS_GELU_SAVE_GRAD;                      // fc1 forward: N = 4608, no remainder column
+    else if (p.act == 4 && p.colsum) { g.epi = PERS_MUL_AUX_COLSUM; g.rm = half ? 2 : 0; }
+    else if (layout == 0 && p.act == 1 && !p.out2 && !p.colsum && !half) g.epi = PERS_GELU;
+    else g.epi = PERS_GENERIC;
+    return 0;
+  }
+  // fp32 weight gradients (TN, split-K slabs / single-slice read-modify-write / plain store): the same persistent kernel
+  if (layout == 2 && pers_ok && p.outf && !p.out && !p.bias && p.act == 0 && p.accumulate != 1 && !p.colsum) { g.family = GemmFamily::pers; g.rm = hc ? 1 : 0; return 0; }
+  // bf16-only outputs of the forward / dX GEMMs take the LDS-staged, fully coalesced epilogue (separate kernel instances, so
+  // neither epilogue's registers burden the other); two outputs: the direct epilogue, as for fp32, and there the column sums are not fused
+  const bool dual = (p.act == 1 && p.out2 != nullptr) || p.act == 3;
+  g.family = GemmFamily::glds; g.tile = tile;
+  g.epi = layout != 2 && bf16_only && !dual && !k.no_staged ? GLDS_STAGED : GLDS_DIRECT;
+  g.colsum_pass_after = g.epi == GLDS_DIRECT && p.colsum != nullptr;
+  return 0;
+}
+int plan_gemm(const pxa_gemm_args* a, GemmParams& p, GemmPlan& g) {     // steps 1-3 of pxa_gemm and the whole of pxa_gemm_plan
+  const GemmKnobs k = read_gemm_knobs();
+  int tile;
+  const int rc = fill_gemm(a, k, p, tile);
+  return rc ? rc : choose_gemm(p, a->layout, p.split, tile, k, g);
+}
+
+template <int LAYOUT, int EPI, int RM, bool SEG>
+int launch_pers(GemmParams p, int split, hipStream_t s) {
+  static_assert(!SEG || LAYOUT == 0, "segmented A: layout NT");
+  p.split = split; constexpr int LDSP = 4 * 40960;                      // the ring (4 x 40 KiB slots) = the CU's whole 160 KiB: one workgroup per CU
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), LDSP);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_pers<%d,%d>): %s", LAYOUT, EPI, hipGetErrorString(e)); return -3; }
+  static int n_cu = 0;                                 // (one kind of device per process)
+  if (!n_cu) {
+    int dev = 0; hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { pxa_set_error("gemm_pers: device query failed"); return -3; }
+    n_cu = prop.multiProcessorCount;
+  }
+  const int tiles = pers_tiles(p.M, p.N, RM) * split;
+  p.sched_slot = dynamic_items() ? (int)(g_launch_seq.fetch_add(1u) & 63u) : -1;
+  hipLaunchKernelGGL((gemm_pers_kernel<LAYOUT, EPI, RM, SEG>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), LDSP, s, p);
+  PXA_LAUNCH_CHECK(); return 0;
+}
+template <int LAYOUT, int TBM, int TBN, int WM, int WN, int EPI, bool SEG>
+int launch_glds_e(GemmParams p, int split, hipStream_t s) {
+  p.split = split; constexpr int LDSG = 2 * (TBM + TBN) * 128;
+  static_assert(WM * WN * (TBM / WM) * EPI_STRIDE <= LDSG, "staged epilogue must fit the operand stages");
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), LDSG);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm_glds<%d,%d,%d>): %s", LAYOUT, TBM, TBN, hipGetErrorString(e)); return -3; }
+  dim3 grid(((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN) * split, 1, 1);
+  hipLaunchKernelGGL((gemm_glds_kernel<LAYOUT, TBM, TBN, WM, WN, EPI, SEG>), grid, dim3(WM * WN * 64), LDSG, s, p);
+  PXA_LAUNCH_CHECK(); return 0;
+}
+template <int LAYOUT>
+int launch_simple(GemmParams p, int split, hipStream_t s) {
+  p.split = split; constexpr bool A_KC = (LAYOUT != 2), B_KC = (LAYOUT == 0);
+  constexpr int LDS = 2 * ((A_KC ? KC_BYTES : RC_BYTES) + (B_KC ? KC_BYTES : RC_BYTES));
+  hipError_t e = lds_optin(reinterpret_cast<const void*>(gemm_kernel<LAYOUT>), LDS);
+  if (e != hipSuccess) { pxa_set_error("hipFuncSetAttribute(gemm<%d>, %d): %s", LAYOUT, LDS, hipGetErrorString(e)); return -3; }
+  dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * split, 1, 1);
+  hipLaunchKernelGGL(gemm_kernel<LAYOUT>, grid, dim3(256), LDS, s, p);
+  PXA_LAUNCH_CHECK(); return 0;
+}
+// Plan -> template instance: the only place that names kernel instances.  Every instance listed is compiled whether or not choose_gemm can reach it
+// (DESIGN.md 0b lists the unreachable ones): in this toolchain the set of instances of a translation unit can change the code of the others.
+int launch_instance(const GemmPlan& g, GemmParams p, hipStream_t s) {
+#define PXA_KEY(f, l, t, e, r, sg) ((((((int)(f) * 3 + (l)) * 3 + (t)) * 8 + (e)) * 3 + (r)) * 2 + ((sg) ? 1 : 0))
+#define PXA_SIMPLE(L) case PXA_KEY(GemmFamily::simple, L, 0, 0, 0, false): return launch_simple<L>(p, g.split, s);
+#define PXA_GLDS(L, T, TBM, TBN, WM, WN, E, SG) case PXA_KEY(GemmFamily::glds, L, T, E, 0, SG): return launch_glds_e<L, TBM, TBN, WM, WN, E, SG>(p, g.split, s);
+#define PXA_GLDS3(L, E) PXA_GLDS(L, 0, 128, 128, 2, 2, E, false) PXA_GLDS(L, 1, 256, 128, 4, 2, E, false) PXA_GLDS(L, 2, 256, 256, 2, 4, E, false)
+#define PXA_PERS(L, E, RM, SG) case PXA_KEY(GemmFamily::pers, L, 0, E, RM, SG): return launch_pers<L, E, RM, SG>(p, g.split, s);
+#define PXA_TOKEN(L) PXA_PERS(L, PERS_PLAIN, 0, false) PXA_PERS(L, PERS_PLAIN, 2, false) PXA_PERS(L, PERS_GELU_SAVE_GRAD, 0, false) PXA_PERS(L, PERS_MUL_AUX_COLSUM, 0, false) PXA_PERS(L, PERS_MUL_AUX_COLSUM, 2, false) PXA_PERS(L, PERS_GENERIC, 0, false)
+#define PXA_CONV(E) PXA_PERS(0, E, 0, true) PXA_PERS(0, E, 1, true) PXA_PERS(0, E, 2, true)
+  if (g.colsum_pass_after) p.colsum = nullptr;
+  switch (PXA_KEY(g.family, g.layout, g.tile, g.epi, g.rm, g.seg)) {
+    PXA_SIMPLE(0) PXA_SIMPLE(1) PXA_SIMPLE(2) PXA_GLDS3(0, GLDS_DIRECT) PXA_GLDS3(0, GLDS_STAGED) PXA_GLDS3(1, GLDS_DIRECT) PXA_GLDS3(1, GLDS_STAGED)
+    PXA_GLDS3(2, GLDS_DIRECT) PXA_GLDS3(2, GLDS_STAGED) PXA_GLDS(0, 0, 128, 128, 2, 2, GLDS_DIRECT, true) PXA_GLDS(0, 0, 128, 128, 2, 2, GLDS_STAGED, true) PXA_TOKEN(0) PXA_TOKEN(1)
+    PXA_PERS(0, PERS_GELU, 0, false) PXA_PERS(2, PERS_PLAIN, 0, false) PXA_PERS(2, PERS_PLAIN, 1, false) PXA_CONV(PERS_PLAIN) PXA_CONV(PERS_ADD_AUX) PXA_CONV(PERS_STATS) PXA_CONV(PERS_ADD_AUX_STATS)
+  }
+  pxa_set_error("pxa_gemm: no kernel instance for the chosen plan"); return -2;       // (choose_gemm names compiled instances only: tests/test_gemm_plan.py)
+}
+
+// out[m][n] += sum_z slab[z][m][n]   (split-K combine at the launch boundary: plain 16-byte loads/stores, no atomics)
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int ld, int M, int N, int split) {
+  const long i4 = blockIdx.x * 256L + threadIdx.x, n4 = N / 4;
+  if (i4 >= (long)M * n4) return;
+  const int m = i4 / n4, n = (i4 - (long)m * n4) * 4;
+  float4 s = *reinterpret_cast<const float4*>(out + (size_t)m * ld + n);
+  for (int z = 0; z < split; z++) {
+    const float4 v = *reinterpret_cast<const float4*>(slab + ((size_t)z * M + m) * N + n);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  *reinterpret_cast<float4*>(out + (size_t)m * ld + n) = s;
+}
+}  // namespace
+
+extern "C" int pxa_gemm(const pxa_gemm_args* a, hipStream_t stream) {
+  GemmParams p; GemmPlan g;
+  int rc = plan_gemm(a, p, g);
+  if (rc) return rc;
+  if (g.try_nt4 && (rc = pxa_gemm_nt4_launch(p, stream)) <= 0) return rc;      // (one k-slice here) 1 = "not mine": on to the kernel of the plan
+  rc = launch_instance(g, p, stream);
+  if (rc == 0 && g.colsum_pass_after) rc = pxa_colsum_bf16(p.out, p.ldo, p.colsum, p.M, p.N, stream);
   if (rc == 0 && p.accumulate == 3) {
-    const long n4 = (long)a->M * (a->N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, stream, p.slab, a->out_f32, a->ld_f32, a->M, a->N, split);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(((long)p.M * (p.N / 4) + 255) / 256), dim3(256), 0, stream, p.slab, p.outf, p.ldf, p.M, p.N, p.split);
     PXA_LAUNCH_CHECK();
   }
   return rc;
 }
 
+extern "C" int pxa_gemm_plan(const pxa_gemm_args* a, char* out, int out_len) {
+  GemmParams p; GemmPlan g;
+  const int rc = plan_gemm(a, p, g);
+  if (rc) return rc;
+  PXA_CHECK(out && out_len > 0, "pxa_gemm_plan: no text buffer");
+  static const int dims[3][4] = {{128, 128, 2, 2}, {256, 128, 4, 2}, {256, 256, 2, 4}};
+  const int* d = dims[g.tile];
+  char inst[64];
+  const char* seg = g.seg ? "true" : "false";
+  if (g.family == GemmFamily::pers) snprintf(inst, sizeof inst, "gemm_pers_kernel<%d,%d,%d,%s>", g.layout, g.epi, g.rm, seg);
+  else if (g.family == GemmFamily::simple) snprintf(inst, sizeof inst, "gemm_kernel<%d>", g.layout);
+  else snprintf(inst, sizeof inst, "gemm_glds_kernel<%d,%d,%d,%d,%d,%d,%s>", g.layout, d[0], d[1], d[2], d[3], g.epi, seg);
+  // split = the k-slices that k_per_split, the accumulate mode and the reduce refer to (fill_gemm's count)
+  const int n = snprintf(out, out_len, "%s split=%d k_per_split=%d accumulate=%d try_nt4=%d colsum_pass_after=%d splitk_reduce=%d", inst, p.split, p.k_per_split, p.accumulate,
+                         g.try_nt4 ? 1 : 0, g.colsum_pass_after ? 1 : 0, p.accumulate == 3 ? 1 : 0);
+  PXA_CHECK(n < out_len, "pxa_gemm_plan: text buffer of %d bytes is too small", out_len);
+  return 0;
+}
+
+
 extern "C" long pxa_gemm_splitk_ws_elems(int M, int N) { return 16L * M * N; }
 
 extern "C" int pxa_gemm_set_dynamic_items(int on) {
   const bool prev = dynamic_items();
-  if (getenv("PXA_GEMM_STATIC") == nullptr && getenv("PXA_GEMM_DYNAMIC") == nullptr) g_dynamic_items.store(on ? 1 : 0);     // (an A/B environment override wins)
+  if (dynamic_items_env() < 0) g_dynamic_items.store(on ? 1 : 0);     // (an A/B environment override wins)
   return prev ? 1 : 0;
 }
 

@@ -13,7 +13,7 @@ OPERAND = os.environ.get("PXA_OPERAND_DTYPE", "bf16").lower()
 assert OPERAND in ("bf16", "f16"), f"PXA_OPERAND_DTYPE must be bf16 or f16, got {OPERAND!r}"
 OPERAND_DTYPE = torch.float16 if OPERAND == "f16" else torch.bfloat16
 LIB_PATH = os.environ.get("PXA_LIB_PATH") or os.path.join(_HERE, "libpixart_hip_f16.so" if OPERAND == "f16" else "libpixart_hip.so")   # env override: A/B kernel builds
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 c_void_p, c_int, c_long, c_float = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -113,7 +113,7 @@ SIGNATURES = {
     "pxa_vae_grid_to_nchw": [_G, _I, _P, _P],
     "pxa_vae_conv3x3_small_out": [_G, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P],
 }
-OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items",
+OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan",
                  "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe"]
 
 _lib = None
@@ -141,6 +141,7 @@ def load():
     lib.pxa_device_info.argtypes, lib.pxa_device_info.restype = [C.POINTER(c_int), C.POINTER(c_int)], c_int
     lib.pxa_attn_bwd_stats_bytes.argtypes, lib.pxa_attn_bwd_stats_bytes.restype = [c_int, c_int, c_int], c_long
     lib.pxa_gemm_set_dynamic_items.argtypes, lib.pxa_gemm_set_dynamic_items.restype = [c_int], c_int
+    lib.pxa_gemm_plan.argtypes, lib.pxa_gemm_plan.restype = [C.POINTER(GemmArgs), C.c_char_p, c_int], c_int
     lib.pxa_mfma_rate_probe_bytes.argtypes, lib.pxa_mfma_rate_probe_bytes.restype = [], c_long
     lib.pxa_mfma_rate_probe.argtypes, lib.pxa_mfma_rate_probe.restype = [c_void_p, c_int, c_int, c_void_p, C.POINTER(C.c_double), c_void_p], c_int
     if lib.pxa_abi_version() != ABI_VERSION:
@@ -161,11 +162,11 @@ def stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
+def ptr(t, cuda=True):
+    """Device pointer of a tensor (None -> NULL).  cuda=False: any tensor's address, for calls that only look at which pointers are set (ops.gemm_plan)."""
     if t is None:
         return None
-    assert t.is_cuda, "pixart_sigma_amd ops need tensors on the MI355X (no CPU fallback)"
+    assert t.is_cuda or not cuda, "pixart_sigma_amd ops need tensors on the MI355X (no CPU fallback)"
     return c_void_p(t.data_ptr())
 
 

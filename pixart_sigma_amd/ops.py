@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (pixart_sigma_amd/lib.py).  Each function validates shapes/dtypes, allocates
 outputs with torch (device memory + stream plumbing only) and launches exactly one libpixart_hip.so entry point.
 No math happens in Python."""
+import ctypes as C
 import math
 
 import torch
@@ -16,8 +17,8 @@ ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_SAVE_GRAD, ACT_MUL_AUX, ACT_ADD_AUX 
 _SPLITK_WS = {}
 
 
-def _chk(t, dtype, name):
-    assert t.is_cuda and t.dtype == dtype and t.stride(-1) == 1, f"{name}: need contiguous-last-dim {dtype} CUDA tensor"
+def _chk(t, dtype, name, cuda=True):
+    assert (t.is_cuda or not cuda) and t.dtype == dtype and t.stride(-1) == 1, f"{name}: need contiguous-last-dim {dtype} CUDA tensor"
 
 
 def gemm(a, b, layout=NT, bias=None, act=ACT_NONE, aux=None, out=None, out2=None, out_f32=None, accumulate=False,
@@ -31,8 +32,54 @@ def gemm(a, b, layout=NT, bias=None, act=ACT_NONE, aux=None, out=None, out2=None
     whose A operand was just written by a kernel that swept the rows upwards; bit-identical results.
     up = (row_pitch, img_rows, dy, dx) of the HIGH-RES padded output grid: this launch is phase (dy, dx) of a 3x3 convolution over a 2x nearest-upsampled
     input, computed on the low-res grid (pxa_gemm_args.up_*); `out` must be given (its rows are high-res padded pixels)."""
-    _chk(a, BF16, "A")
-    _chk(b, BF16, "B")
+    g, res = _gemm_args(False, **locals())         # (locals() = the arguments, nothing else yet)
+    call("pxa_gemm", g)
+    return res
+
+
+def gemm_plan(a, b, layout=NT, bias=None, act=ACT_NONE, aux=None, out=None, out2=None, out_f32=None, accumulate=False,
+              split_k=1, out_dtype=BF16, colsum=None, k_seg=0, a_seg_stride=0, k_tap=0, gn_part=None, gn_geom=None, descending=False, up=None):
+    """What gemm would launch for the same arguments, as pxa_gemm_plan's one line of text (kernel instance, split, k_per_split, accumulate mode, ...); raises
+    what gemm would raise for a call the library refuses.  Launches nothing, allocates nothing and needs no GPU: the tensors may live on any device (only
+    their shapes, strides and the presence of each pointer matter)."""
+    g, _ = _gemm_args(True, **locals())
+    buf = C.create_string_buffer(256)
+    lib.check(lib.load().pxa_gemm_plan(C.byref(g), buf, len(buf)), "pxa_gemm_plan")
+    return buf.value.decode()
+
+
+class _Unallocated:
+    """gemm_plan's stand-in for a buffer gemm would allocate: rows x cols of a dtype at an address that is not NULL and never used."""
+    _somewhere = C.c_double()
+
+    def __init__(self, rows, cols, dtype):
+        self.shape, self.dtype = (rows, cols), dtype
+
+    def __getitem__(self, i):
+        return self
+
+    def stride(self, d):
+        return (self.shape[1], 1)[d]
+
+    def numel(self):
+        return self.shape[0] * self.shape[1]
+
+
+def _gemm_args(plan, a, b, layout, bias, act, aux, out, out2, out_f32, accumulate, split_k, out_dtype, colsum, k_seg, a_seg_stride, k_tap, gn_part, gn_geom,
+               descending, up):
+    """The pxa_gemm_args block of gemm / gemm_plan and the tensor gemm returns.  gemm allocates the outputs and the split-K workspace that are not given;
+    plan = True (gemm_plan) only says where they would be, and the tensors need not be on the GPU."""
+    def chk(t, dtype, name):
+        if not isinstance(t, _Unallocated):
+            _chk(t, dtype, name, cuda=not plan)
+
+    def ptr(t):
+        return C.c_void_p(C.addressof(t._somewhere)) if isinstance(t, _Unallocated) else lib.ptr(t, cuda=not plan)
+
+    def new(rows, cols, dtype):
+        return _Unallocated(rows, cols, dtype) if plan else torch.empty((rows, cols), dtype=dtype, device=a.device)
+    chk(a, BF16, "A")
+    chk(b, BF16, "B")
     if layout == NT:
         M, K = a.shape
         N, K2 = b.shape
@@ -47,33 +94,33 @@ def gemm(a, b, layout=NT, bias=None, act=ACT_NONE, aux=None, out=None, out2=None
     g.A, g.B, g.lda, g.ldb = ptr(a), ptr(b), a.stride(0), b.stride(0)
     g.M, g.N, g.K, g.layout = M, N, K, layout
     if bias is not None:
-        _chk(bias, F32, "bias")
+        chk(bias, F32, "bias")
         assert bias.numel() == N
     g.bias, g.act = ptr(bias), act
     if act in (ACT_GELU_GRAD, ACT_MUL_AUX, ACT_ADD_AUX):
-        _chk(aux, BF16, "aux")
+        chk(aux, BF16, "aux")
         g.aux, g.ldaux = ptr(aux), aux.stride(0)
     want_f32 = out_f32 is not None or out_dtype == F32
     if want_f32:
         if out_f32 is None:
-            out_f32 = torch.empty((M, N), dtype=F32, device=a.device)
-        _chk(out_f32, F32, "out_f32")
+            out_f32 = new(M, N, F32)
+        chk(out_f32, F32, "out_f32")
         g.out_f32, g.ld_f32 = ptr(out_f32), out_f32.stride(0)
     else:
         if out is None:
-            out = torch.empty((M, N), dtype=BF16, device=a.device)
+            out = new(M, N, BF16)
     if out is not None:
-        _chk(out, BF16, "out")
+        chk(out, BF16, "out")
         g.out_bf16, g.ld_out = ptr(out), out.stride(0)
     if out2 is not None:
-        _chk(out2, BF16, "out2")
+        chk(out2, BF16, "out2")
         assert out is not None and out2.stride(0) == out.stride(0)
         g.out2_bf16 = ptr(out2)
     g.accumulate, g.split_k = int(accumulate), split_k
     g.items_descending = int(bool(descending))
     g.k_seg, g.a_seg_stride, g.k_tap = k_seg, a_seg_stride, k_tap
     if gn_part is not None:
-        _chk(gn_part, F32, "gn_part")
+        chk(gn_part, F32, "gn_part")
         assert gn_part.is_contiguous() and gn_part.numel() == COLSUM_SLOTS * (M // gn_geom[0]) * (N // 4) * 2
         g.gn_part = ptr(gn_part)
         g.gn_img_rows, g.gn_row_pitch, g.gn_h, g.gn_w = gn_geom
@@ -86,10 +133,11 @@ def gemm(a, b, layout=NT, bias=None, act=ACT_NONE, aux=None, out=None, out2=None
         need = 16 * M * N
         ws = _SPLITK_WS.get(a.device)
         if ws is None or ws.numel() < need:
-            ws = _SPLITK_WS[a.device] = torch.empty(need, dtype=F32, device=a.device)
+            ws = new(1, need, F32)[0]
+            if not plan:
+                _SPLITK_WS[a.device] = ws
         g.splitk_ws, g.splitk_ws_elems = ptr(ws), ws.numel()
-    call("pxa_gemm", g)
-    return out_f32 if want_f32 else out
+    return g, (out_f32 if want_f32 else out)
 
 
 def ln_mod_fwd(x, shift=None, scale=None, mod_stride=0, u=None, gate=None, gate_stride=None, x_out=None, want_xn=True, want_xb=False,

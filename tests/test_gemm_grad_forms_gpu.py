@@ -121,6 +121,12 @@ def surviving_slices(K, split_k):
     return (K + kps - 1) // kps, kps
 
 
+def plan_of(ops, a, b, layout, **kw):
+    """ops.gemm_plan of a call as a dict: "kernel" = the instance as its template is written, the other fields as integers."""
+    w = ops.gemm_plan(a, b, layout, **kw).split()
+    return dict(kernel=w[0], **{k: int(v) for k, v in (kv.split("=") for kv in w[1:])})
+
+
 def tn_operands(M, N, K):
     """dW[M][N] = sum_k A[k][M] B[k][N]: (a, b, fp64 reference)."""
     a, b = bf(_gpu_rnd(K, M, seed=1)), bf(_gpu_rnd(K, N, seed=2))
@@ -161,7 +167,8 @@ def test_weight_gradient_accumulate(ops, M, N, K, cls):
               read-modify-write (accumulate mode 2); K = 7 is less than one k-tile.
       model   the same operands with K % 64 == 0: the (tile, split) cost model decides (engine.py, block_bwd: the kv_linear comment).
       m32     final layer, M = 32 < 256: only the 128-tile candidate is legal, 96 of 128 tile rows are beyond M.
-      remX    N % 256 == 128: the paired remainder column of the persistent TN kernel, odd (5, 9) and even (14) m-tile counts, at mid K.
+      remX    N % 256 == 128: the paired remainder column of the persistent TN kernel, odd (9) and even (14) m-tile counts, at mid K; at 5 m-tiles the cost
+              model picks the 128 x 128 kernel instead (asserted below through ops.gemm_plan, as is every kernel this docstring names).
       norem   N % 256 == 0."""
     assert M % 8 == 0 and N % 8 == 0
     if cls == "ragged":
@@ -176,6 +183,15 @@ def test_weight_gradient_accumulate(ops, M, N, K, cls):
         assert N % 256 == 0 and M >= 256
     a, b, ref = tn_operands(M, N, K)
     out = Banded(M, N, torch.float32, MINUS_ZERO32)
+    plan = plan_of(ops, a, b, ops.TN, out_f32=out.view, accumulate=True, split_k=0)
+    if cls == "ragged":
+        assert (plan["kernel"], plan["split"], plan["accumulate"], plan["splitk_reduce"]) == ("gemm_kernel<2>", 1, 2, 0), plan
+    if cls == "m32":
+        assert plan["kernel"] == "gemm_glds_kernel<2,128,128,2,2,0,false>", plan
+    if cls.startswith("rem"):          # (rem5: the cost model prefers 128 x 128 tiles for 5 x 5 padded 256 tiles at this K; its remainder column is the 128 kernel's)
+        assert plan["kernel"] == ("gemm_glds_kernel<2,128,128,2,2,0,false>" if cls == "rem5" else "gemm_pers_kernel<2,0,1,false>"), plan
+    if cls == "norem":
+        assert plan["kernel"] == "gemm_pers_kernel<2,0,0,false>", plan
     accumulate_twice(ops, f"TN dW {M}x{N} K={K} {cls}", a, b, ops.TN, out, ref, split_k=0, poison=True)
 
 
@@ -188,6 +204,11 @@ def test_explicit_split_counts(ops, K, split_k, slices, slice_k):
     assert surviving_slices(K, split_k) == (slices, slice_k) and (slices - 1) * slice_k < K <= slices * slice_k
     a, b, ref = tn_operands(M, N, K)
     out = Banded(M, N, torch.float32, MINUS_ZERO32)
+    poison_splitk_workspace(ops, a, M, N)                   # (so that the plan sees the workspace the calls below get)
+    plan = plan_of(ops, a, b, ops.TN, out_f32=out.view, accumulate=True, split_k=split_k)
+    assert (plan["split"], plan["k_per_split"]) == (slices, slice_k), plan
+    assert (plan["accumulate"], plan["splitk_reduce"]) == ((2, 0) if slices == 1 else (3, 1)), plan
+    assert plan["kernel"] == ("gemm_kernel<2>" if K % BK else "gemm_pers_kernel<2,0,1,false>"), plan
     accumulate_twice(ops, f"TN {M}x{N} K={K} split_k={split_k} ({slices} slices)", a, b, ops.TN, out, ref, split_k=split_k, poison=True)
     assert ops._SPLITK_WS[a.device].numel() >= slices * M * N
 
@@ -204,6 +225,8 @@ def test_atomic_accumulate_when_workspace_is_short(ops):
     try:
         accumulate_twice(ops, f"TN {M}x{N} K={K} split_k={split_k} atomics", a, b, ops.TN, out, ref, split_k=split_k, poison=False)
         assert ops._SPLITK_WS[a.device].numel() < 17 * M * N, "the workspace held all 17 slabs: this case did not reach the atomic mode"
+        plan = plan_of(ops, a, b, ops.TN, out_f32=out.view, accumulate=True, split_k=split_k)
+        assert (plan["split"], plan["accumulate"], plan["splitk_reduce"]) == (17, 1, 0), plan
     finally:
         cur = ops._SPLITK_WS.get(a.device)
         if saved is not None and (cur is None or saved.numel() > cur.numel()):
@@ -258,6 +281,7 @@ def test_final_layer_f32(ops, M):
     ref = a.double() @ w.double().t() + b.double()
     out = Banded(M, N, torch.float32, SENTINEL32)
     out.view.fill_(float("nan"))
+    assert plan_of(ops, a, w, ops.NT, bias=b, out_f32=out.view)["kernel"] == "gemm_glds_kernel<0,128,128,2,2,0,false>"
     ops.gemm(a, w, ops.NT, bias=b, out_f32=out.view)
     torch.cuda.synchronize()
     out.assert_intact(f"NT final {M}x{N} K={K}")
@@ -276,6 +300,7 @@ def test_final_layer_input_gradient(ops, M):
     ref = dy.double() @ w.double()
     out = Banded(M, N, _opd(), SENTINEL16)
     out.view.fill_(float("nan"))
+    assert plan_of(ops, dy, w, ops.NN, out=out.view, descending=True)["kernel"] == "gemm_kernel<1>"
     ops.gemm(dy, w, ops.NN, out=out.view, descending=True)
     torch.cuda.synchronize()
     out.assert_intact(f"NN final dx {M}x{N} K={K}")
@@ -301,7 +326,9 @@ def test_caption_fc1_forward_ragged_rows(ops, M):
     out, out2 = Banded(M, N, _opd(), SENTINEL16), Banded(M, N, _opd(), SENTINEL16)
     out.view.fill_(float("nan"))
     out2.view.fill_(float("nan"))
-    ops.gemm(a, w, ops.NT, bias=b, act=ops.ACT_GELU_SAVE_GRAD, out=out.view, out2=out2.view, descending=False)
+    call = dict(bias=b, act=ops.ACT_GELU_SAVE_GRAD, out=out.view, out2=out2.view, descending=False)
+    assert plan_of(ops, a, w, ops.NT, **call)["kernel"] == ("gemm_glds_kernel<0,128,128,2,2,0,false>" if M < 1024 else "gemm_pers_kernel<0,1,0,false>")
+    ops.gemm(a, w, ops.NT, **call)
     torch.cuda.synchronize()
     out.assert_intact(f"NT caption fc1 {M} rows: out")
     out2.assert_intact(f"NT caption fc1 {M} rows: out2")
@@ -319,7 +346,9 @@ def test_caption_fc2_input_gradient_ragged_rows(ops, M):
     ref = (dy.double() @ w.double()) * aux.double()
     out = Banded(M, N, _opd(), SENTINEL16)
     out.view.fill_(float("nan"))
-    ops.gemm(dy, w, ops.NN, act=ops.ACT_MUL_AUX, aux=aux, out=out.view, descending=False)
+    call = dict(act=ops.ACT_MUL_AUX, aux=aux, out=out.view, descending=False)
+    assert plan_of(ops, dy, w, ops.NN, **call)["kernel"] == ("gemm_glds_kernel<1,128,128,2,2,1,false>" if M < 1024 else "gemm_pers_kernel<1,3,0,false>")
+    ops.gemm(dy, w, ops.NN, **call)
     torch.cuda.synchronize()
     out.assert_intact(f"NN caption fc2 dx {M} rows")
     check_16(f"NN caption fc2 dx {M}x{N} K={K} x aux", out.view, ref)

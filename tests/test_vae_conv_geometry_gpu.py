@@ -70,6 +70,17 @@ def model_tol(ops):
     return F16_VAE_TOL if ops.BF16 == torch.float16 else MODEL_TOL
 
 
+def conv_instance(M, N, epi):
+    """The kernel instance pxa_gemm gives an implicit convolution of M rows and N channels with epilogue `epi` (file header; csrc/gemm.hip, choose_gemm): the
+    persistent kernel from 1024 rows on, its remainder column (N % 256 == 128) as PAIRED items (RM 1) or, under PXA_GEMM_SEG_HALF, HALF items (RM 2); below
+    1024 rows the two-stage 128 x 128 kernel, staged epilogue without a residual, direct with one.  Assumes no other dispatch knob is set
+    (PXA_GEMM_NO_PERSISTENT would send every case to the two-stage kernel and fail these asserts, not the numbers)."""
+    if M < 1024:
+        return f"gemm_glds_kernel<0,128,128,2,2,{int(epi == 0)},true>"
+    rm = 0 if N % 256 == 0 else 2 if os.environ.get("PXA_GEMM_SEG_HALF") else 1
+    return f"gemm_pers_kernel<0,{epi},{rm},true>"
+
+
 def img_rows(H, W):
     from pixart_sigma_amd.vae.autoencoder_kl import _img_rows
     return _img_rows(H, W)
@@ -194,8 +205,10 @@ def test_implicit_conv_guarded(ops, case):
     res = (rnd(M, Co, seed=4) * 3.0).to(ops.BF16) if residual else None
     whole, out = banded_rows(ops, M, Co)
     flat, part = banded_part(ops, B, Co) if stats else (None, None)
-    got = ops.gemm(a, wk, ops.NT, bias=bias, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, act=ops.ACT_ADD_AUX if residual else ops.ACT_NONE, aux=res,
-                   gn_part=part, gn_geom=(ip, rp, H, W) if stats else None)
+    call = dict(bias=bias, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, act=ops.ACT_ADD_AUX if residual else ops.ACT_NONE, aux=res,
+                gn_part=part, gn_geom=(ip, rp, H, W) if stats else None)
+    assert ops.gemm_plan(a, wk, ops.NT, **call).split()[0] == conv_instance(M, Co, epi)
+    got = ops.gemm(a, wk, ops.NT, **call)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
     label = case_id(case)
@@ -230,7 +243,9 @@ def test_masked_statistics_adds_clear_the_sign_of_minus_zero(ops):
     flat, part = banded_part(ops, B, Co)
     part[2:14] = -0.0
     assert (part[2:14].view(torch.int32) == -(1 << 31)).all()
-    ops.gemm(a, wk, ops.NT, bias=bias, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, gn_part=part, gn_geom=(ip, rp, H, W))
+    call = dict(bias=bias, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, gn_part=part, gn_geom=(ip, rp, H, W))
+    assert ops.gemm_plan(a, wk, ops.NT, **call).split()[0] == conv_instance(B * ip, Co, 5)
+    ops.gemm(a, wk, ops.NT, **call)
     torch.cuda.synchronize()
     bits = part.view(torch.int32)
     kept = int((bits[2:14] == -(1 << 31)).sum())
@@ -258,6 +273,8 @@ def test_statistics_below_1024_rows_are_refused(ops):
     flat, part = banded_part(ops, B, Co)
     with pytest.raises(PixartHipError, match="gn_part needs the persistent implicit-convolution path"):
         ops.gemm(a, wk, ops.NT, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, gn_part=part, gn_geom=(ip, rp, H, W))
+    with pytest.raises(PixartHipError, match="gn_part needs the persistent implicit-convolution path"):      # the plan of the same call is refused alike
+        ops.gemm_plan(a, wk, ops.NT, out=out, k_seg=3 * C, a_seg_stride=rp * C, k_tap=C, gn_part=part, gn_geom=(ip, rp, H, W))
     torch.cuda.synchronize()
     assert (whole.view(torch.int16) == SENTINEL).all() and (part == 0).all()
     assert_part_bands_untouched(flat, B, Co, "refused")
@@ -289,7 +306,9 @@ def test_phase_convolution_scatter_guarded(ops, B, H, W, Co, want_mt):
     for i, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
         off = (W + 3) + (dy - 1) * rpL + dx - 1
         a = buf.as_strided((B * ipL, 4 * C), (C, 1), off * C)
-        ops.gemm(a, phases[i], ops.NT, bias=bias, out=out, k_seg=2 * C, a_seg_stride=rpL * C, gn_part=part, gn_geom=(ipL, rpL, H, W), up=(rpH, ipH, dy, dx))
+        call = dict(bias=bias, out=out, k_seg=2 * C, a_seg_stride=rpL * C, gn_part=part, gn_geom=(ipL, rpL, H, W), up=(rpH, ipH, dy, dx))
+        assert ops.gemm_plan(a, phases[i], ops.NT, **call).split()[0] == conv_instance(B * ipL, Co, 5)
+        ops.gemm(a, phases[i], ops.NT, **call)
     torch.cuda.synchronize()
     label = f"phase conv B{B} {H}x{W} C{Co} mt{want_mt}"
     assert_row_bands_untouched(whole, label)
