@@ -330,8 +330,10 @@ __device__ __forceinline__ void epilogue_staged(const GemmParams& p, f32x16 (&ac
               }
             }
           }
-          *reinterpret_cast<uint2*>(wl + (i * 32 + (lane & 31)) * EPI_STRIDE + (((col >> 3) ^ (lane & 7)) << 4) + (col & 4) * 2) = pack_bf16x4(v[0], v[1], v[2], v[3]);
-          if (pass == 1 && p.colsum && mw + i * 32 + (lane & 31) < p.M) {
+          const uint2 pk = pack_bf16x4(v[0], v[1], v[2], v[3]);
+          *reinterpret_cast<uint2*>(wl + (i * 32 + (lane & 31)) * EPI_STRIDE + (((col >> 3) ^ (lane & 7)) << 4) + (col & 4) * 2) = pk;
+          if (pass == 1 && p.colsum && mw + i * 32 + (lane & 31) < p.M) {        // the column sums are those of the STORED (rounded) values, as in every other path
+            unpack_bf16x2(pk.x, v[0], v[1]); unpack_bf16x2(pk.y, v[2], v[3]);
 #pragma unroll
             for (int e = 0; e < 4; e++) cs[j][q * 4 + e] += v[e];
           }

@@ -4,7 +4,9 @@ are read once per process run in a child process each; PXA_GEMM_NO_GLDS is flipp
 
 The expected lines are meant to be the parent commit's behaviour.  So far they rest on reading the parent's dispatch: the kernel-trace
 comparison that is to establish them on a GPU (tools/gemm_dispatch.py under rocprofv3 --kernel-trace at both commits, --check against these plan lines) has not
-been run yet."""
+been run yet.  They additionally rest on values: tests/test_gemm_call_list_gpu.py runs every launched call on the GPU under each setting (default, no_persistent,
+no_half_items, no_staged_epilogue, seg_half, tile_128, tile_256x128, tile_256, no_glds, nt4, and ascending / static_items / dynamic_items with the default
+plans), asserts expected() on the plan line of the very call and compares what the kernel wrote with an fp64 reference."""
 import json
 import os
 import subprocess

@@ -76,7 +76,8 @@ def test_gemm_nn_gelu_grad(ops):
     assert rel_l2(out.float(), ref * x.grad) < BF16_TOL
     cs = torch.ones(N, device="cuda")
     ops.colsum_reduce(part[:, 64:], cs)
-    assert rel_l2(cs, 1 + (ref * x.grad).sum(0)) < 1e-4          # fused bias-gradient column sums (staged epilogue)
+    assert rel_l2(cs, 1 + out.float().sum(0)) < 1e-4             # fused bias-gradient column sums (staged epilogue): over exactly the values that are stored,
+    assert rel_l2(cs, 1 + (ref * x.grad).sum(0)) < 5e-3          # as in every other path (include/pixart_hip.h: "column sums of the bf16 output"), so they carry their rounding
     part.zero_()
     ops.gemm(dy[:, :72], w[:72], ops.NN, colsum=part)                # K=72: register-staged fallback kernel + separate column-sum pass
     assert rel_l2(part.sum(0)[:N], (dy[:, :72].float() @ w[:72].float()).to(_opd()).float().sum(0)) < 1e-4

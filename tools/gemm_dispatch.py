@@ -1,12 +1,14 @@
 """The call list that pins pxa_gemm's host-side dispatch (csrc/gemm.hip: fill_gemm, choose_gemm, launch_instance), and the script that issues it.
 
-    python tools/gemm_dispatch.py                     every call of CASES once on cuda:0, seeded inputs (prints ops.gemm_plan's line per call where the
-                                                      library has it); meant to run under `rocprofv3 --kernel-trace --output-format csv -- python ...`
+    python tools/gemm_dispatch.py                     every call of CASES once on cuda:0, seeded inputs: per call ops.gemm_plan's line, then " | " and the
+                                                      errors of what the call wrote against reference(); also meant to run under
+                                                      `rocprofv3 --kernel-trace --output-format csv -- python ...`
     python tools/gemm_dispatch.py --launches x.csv    the ordered (kernel, grid, workgroup, LDS bytes) list of a kernel-trace csv, GEMM-side kernels only
     python tools/gemm_dispatch.py --check x.csv out   --launches, checked against the plan lines: per call the instance named, then the column-sum pass and
                                                       the split-K reduce where the plan says so (needs no GPU)
 
-CASES is shared with tests/test_gemm_plan.py (the expected plan lines live there).  Each case is (name, dict): layout, M, N, K and what else the call carries.
+CASES is shared with tests/test_gemm_plan.py (the expected plan lines live there) and tests/test_gemm_call_list_gpu.py (the values: prepare_outputs,
+reference and errors below, per setting in a child process each).  Each case is (name, dict): layout, M, N, K and what else the call carries.
 Shapes are the smallest that reach a branch: M = 1024 rows, N = 1024 / 1152 (N % 256 == 128: the remainder column) / 1280, N = 128 / 256 / 384 for the
 convolutions, K of one or two k-units, 4096 for the cost model and explicit splits, 72 for the register-staged kernel.  SETTINGS are the environments the list
 runs under: every once-per-process knob needs a process of its own."""
@@ -146,6 +148,179 @@ def make_call(spec, device, seed=0, values=True):
     return a, b, kw
 
 
+# ------------------------------------------------------------------------------------------------ what a call writes, and what it should have written
+BLOCK = 64                 # rows and columns of the block the errors are taken over: a wave's store tile
+
+
+def written(spec):
+    """the kinds of figures errors() returns for a case: one per output the call writes"""
+    kinds = ["out_f32"] if spec.get("f32") else ["out"]
+    kinds += ["out2"] * bool(spec.get("out2")) + ["colsum_to_stored", "colsum_to_reference"] * bool(spec.get("colsum")) + ["gn_sums", "gn_finalize"] * bool(spec.get("stats"))
+    return kinds
+
+
+def prepare_outputs(spec, a, kw, seed=0):
+    """The outputs of make_call's keyword arguments as a values check wants them before the call: an accumulate target holds seeded N(0, 1) values, every other
+    output is all NaN (the 16-bit `out` the call would allocate is given), so a tile the kernel never writes shows; colsum and gn_part stay zeroed."""
+    import torch
+    from pixart_sigma_amd import ops
+    if spec.get("f32"):
+        t = kw["out_f32"]
+        if kw["accumulate"]:
+            t.copy_(torch.randn(t.shape, generator=torch.Generator().manual_seed(1000 + seed)))
+        else:
+            t.fill_(float("nan"))
+    else:
+        if "out" not in kw:
+            kw["out"] = torch.empty(spec["M"], spec["N"], dtype=ops.BF16, device=a.device)
+        kw["out"].fill_(float("nan"))
+    if "out2" in kw:
+        kw["out2"].fill_(float("nan"))
+    return kw
+
+
+def _geometry():
+    """tests/test_vae_conv_geometry_gpu.py: img_rows, conv_ref64 and check_statistics are stated there, once"""
+    tests = os.path.join(ROOT, "tests")
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import test_vae_conv_geometry_gpu as geo
+    return geo
+
+
+def _conv_rows(spec, device):
+    """(B, H, W) row indices of the interior pixels: in the A operand's padded grid, and in `out` (the 2x grid for a phase of the upsampled convolution)"""
+    import torch
+    B, H, W, _ = spec["conv"]
+    rp, ip = W + 2, _geometry().img_rows(H, W)
+    b, py, px = (torch.arange(n, device=device).view(s) for n, s in ((B, (B, 1, 1)), (H, (1, H, 1)), (W, (1, 1, W))))
+    low = b * ip + (py + 1) * rp + px + 1
+    if "up" not in spec:
+        return low, low
+    dy, dx = spec["up"]
+    return low, b * _geometry().img_rows(2 * H, 2 * W) + (2 * py + 1 + dy) * (2 * W + 2) + 2 * px + 1 + dx
+
+
+def _gelu64(pre):
+    """tanh-GELU and its derivative in fp64"""
+    import torch
+    import torch.nn.functional as F
+    x = pre.clone().requires_grad_(True)
+    y = F.gelu(x, approximate="tanh")
+    y.sum().backward()
+    return y.detach(), x.grad
+
+
+def reference(spec, a, b, kw):
+    """The fp64 expectation of everything the call of make_call(spec) writes, from the 16-bit-rounded operands as they are, on their device (include/pixart_hip.h;
+    tests/test_kernels_gpu.py states the same per epilogue).  Call it before ops.gemm: an accumulate target is read for what it holds.  Returns a dict:
+      "out" / "out2" / "out_f32"   the output's shape in fp64;
+      "rows"                       implicit convolutions only: the rows of the output that are specified (interior pixels; for the phase of an upsampled
+                                   convolution their places in the 2x grid), the others of the expectation are zero and mean nothing;
+      "colsum"                     the column sums of "out" (the kernel's sums are taken over the stored 16-bit values: errors() has both comparisons).
+    The implicit convolutions are F.conv2d in fp64 (conv_ref64 of tests/test_vae_conv_geometry_gpu.py) over the padded pixel grid the A operand is a view of."""
+    import torch
+    M, N, K, layout, act = spec["M"], spec["N"], spec["K"], spec["layout"], kw["act"]
+    bias = kw["bias"].double() if "bias" in kw else torch.zeros(N, dtype=torch.float64, device=a.device)
+    aux = kw["aux"].double() if "aux" in kw else None
+    ref = {}
+    if "conv" in spec:
+        geo = _geometry()
+        B, H, W, C = spec["conv"]
+        rp, ip = W + 2, geo.img_rows(H, W)
+        pix = a.as_strided((a.untyped_storage().nbytes() // a.element_size() // C, C), (C, 1), 0)           # the pixel rows A's patches are views of
+        b_, i_, j_ = (torch.arange(n, device=a.device).view(s) for n, s in ((B, (B, 1, 1)), (H + 3, (1, H + 3, 1)), (rp, (1, 1, rp))))
+        if "up" in spec:         # row m = sum over a 2 x 2 patch from pixel m on, K = [2 rows][2 taps][C]: conv2d (padding 1) of the grid whose (i, j) is pixel i rp + j
+            grid, w, sl = pix[(b_ * ip + i_ * rp + j_)[:, :H + 2]], b.view(N, 2, 2, C).permute(0, 3, 1, 2), (slice(2, H + 2), slice(2, W + 2))
+        else:                    # row m = sum over a 3 x 3 patch from pixel m on, K = [C / 64][3 rows][3 taps][64]: the grid whose (i, j) is pixel i rp + j + 1
+            assert kw["k_tap"] == C and C % 64 == 0
+            grid, w, sl = pix[b_ * ip + i_ * rp + j_ + 1], b.view(N, C // 64, 3, 3, 64).permute(0, 1, 4, 2, 3).reshape(N, C, 3, 3), (slice(2, H + 2), slice(1, W + 1))
+        y = geo.conv_ref64(grid.permute(0, 3, 1, 2), w, bias)[:, :, sl[0], sl[1]].to(a.device)               # (B, N, H, W): the interior pixels
+        low, high = _conv_rows(spec, a.device)
+        y = y.permute(0, 2, 3, 1).reshape(-1, N)
+        if act == 5:
+            y = y + aux[low.flatten()]
+        else:
+            assert act == 0
+        target = kw["out_f32"] if spec.get("f32") else kw["out"]
+        full = torch.zeros(target.shape, dtype=torch.float64, device=a.device)
+        full[high.flatten()] = y
+        ref["out_f32" if spec.get("f32") else "out"] = full
+        ref["rows"] = torch.zeros(target.shape[0], dtype=torch.bool, device=a.device)
+        ref["rows"][high.flatten()] = True
+        assert int(ref["rows"].sum()) == B * H * W
+        return ref
+    A, Bm = a.double(), b.double()
+    pre = (A @ Bm.t() if layout == NT else A @ Bm if layout == NN else A.t() @ Bm) + bias
+    if spec.get("f32"):
+        assert act == 0
+        ref["out_f32"] = pre + kw["out_f32"].double() if kw["accumulate"] else pre
+        return ref
+    if act in (1, 3):
+        ref["out"], grad = _gelu64(pre)
+        if "out2" in kw:
+            ref["out2"] = pre if act == 1 else grad
+    elif act == 2:
+        ref["out"] = pre * _gelu64(aux)[1]
+    else:
+        ref["out"] = pre if act == 0 else pre * aux if act == 4 else pre + aux
+    if "colsum" in kw:
+        ref["colsum"] = ref["out"].sum(0)
+    return ref
+
+
+def block_rel_l2(got, want, rows=None):
+    """(the largest rel-L2 over the BLOCK x BLOCK blocks of a 2-D output, the number of non-finite values): a global rel-L2 dilutes one bad tile of a large
+    output to nothing.  rows: the specified rows (a block's figure is over those only; a block without any has none)."""
+    import torch
+    import torch.nn.functional as F
+    got, want = got.double(), want.double()
+    if got.dim() == 1:
+        got, want = got[None], want[None]
+    if rows is not None:                              # (the blocks stay where the kernel's tiles are)
+        got, want = torch.where(rows[:, None], got, 0.0), torch.where(rows[:, None], want, 0.0)
+    bad = int((~torch.isfinite(got)).sum())
+    R, N = got.shape
+    pad = (0, -N % BLOCK, 0, -R % BLOCK)
+    num = F.pad((got - want) ** 2, pad).view((R + BLOCK - 1) // BLOCK, BLOCK, -1, BLOCK).sum((1, 3))
+    den = F.pad(want ** 2, pad).view((R + BLOCK - 1) // BLOCK, BLOCK, -1, BLOCK).sum((1, 3))
+    e = (num / den.clamp_min(1e-300)).sqrt()
+    return (float("nan") if torch.isnan(e).any() else e.max().item()), bad
+
+
+def errors(spec, kw, ref, statistics=True):
+    """{kind: figure} for every kind of written(spec), after the call: the 2-D outputs as block_rel_l2 against reference(); the column sums (summed over the slots)
+    against the column sums of the STORED 16-bit output and against the reference's; the GroupNorm partials through check_statistics of
+    tests/test_vae_conv_geometry_gpu.py (its two figures; "gn_assert" holds its message where it failed).  "nan": non-finite values found where a value is
+    specified, over all outputs.  statistics = False leaves the partials out (check_statistics finalizes on the GPU)."""
+    out, nan = {}, 0
+    for kind in ("out", "out2", "out_f32"):
+        if kind in ref:
+            out[kind], bad = block_rel_l2(kw[kind], ref[kind], ref.get("rows"))
+            nan += bad
+    if "colsum" in kw:
+        sums = kw["colsum"].double().sum(0)
+        out["colsum_to_stored"], bad = block_rel_l2(sums, kw["out"].double().sum(0))
+        out["colsum_to_reference"], _ = block_rel_l2(sums, ref["colsum"])
+        nan += bad
+    if spec.get("stats") and statistics:
+        import conftest
+        from pixart_sigma_amd import ops
+        geo = _geometry()
+        B, H, W, _ = spec["conv"]
+        y = kw["out"][_conv_rows(spec, kw["out"].device)[1]].permute(0, 3, 1, 2).contiguous()           # the stored interior pixels, (B, N, H, W)
+        first = len(conftest.PARITY)
+        try:
+            geo.check_statistics(ops, kw["gn_part"], y, B, spec["N"], H, W, "call list", fin_tol=geo.PHASE_FIN_TOL if "up" in spec else geo.STAT_FIN_TOL)
+        except AssertionError as e:
+            out["gn_assert"] = str(e)
+        figures = conftest.PARITY[first:]
+        del conftest.PARITY[first:]
+        out["gn_sums"], out["gn_finalize"] = figures[0]["value"], figures[1]["value"]
+    out["nan"] = nan
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ kernel-trace csv -> launches
 GEMM_SIDE = r"gemm_\w*kernel|splitk_reduce_kernel|colsum_kernel"
 
@@ -187,19 +362,26 @@ def main():
         for l in got:
             print(*l)
         if sys.argv[1] == "--check":                                     # argv[3]: the output of the run that was traced
-            plan_lines = [l.split(": ", 1) for l in open(sys.argv[3]).read().splitlines() if ": gemm_" in l]
+            plan_lines = [l.split(" | ")[0].split(": ", 1) for l in open(sys.argv[3]).read().splitlines() if ": gemm_" in l]
             print(f"# {len(got)} launches of {len(plan_lines)} calls: every kernel is the one its plan names ({check(got, plan_lines)} matched by name)")
         return
     import torch
     from pixart_sigma_amd import ops
+    from pixart_sigma_amd.lib import PixartHipError
     for i, (name, spec) in enumerate(CASES):
         if "refused" in spec:
             continue
         a, b, kw = make_call(spec, "cuda:0", seed=i)
-        if hasattr(ops, "gemm_plan"):
-            print(f"{name}: {ops.gemm_plan(a, b, **kw)}", flush=True)
+        prepare_outputs(spec, a, kw, seed=i)
+        try:
+            line = ops.gemm_plan(a, b, **kw)
+        except PixartHipError as e:                                      # (a setting can refuse a call of the list: the plan says so before anything is launched)
+            print(f"{name}: refused: {e}", flush=True)
+            continue
+        ref = reference(spec, a, b, kw)
         ops.gemm(a, b, **kw)
         torch.cuda.synchronize()
+        print(f"{name}: {line} | " + " ".join(f"{k} {v:.2e}" if isinstance(v, float) else f"{k} {v}" for k, v in errors(spec, kw, ref).items()), flush=True)
     print("# done")
 
 
