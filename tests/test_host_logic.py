@@ -285,3 +285,43 @@ def test_keys_resident_attention_refuses_a_sample_longer_than_max_kv_len():
     from pixart_sigma_amd import engine
     src = inspect.getsource(engine.Engine)
     assert src.count("kv_len_host=ctx.get(\"lens_host\")") == 2          # both cross-attention call sites pass the host lengths
+
+
+def test_small_kernel_edge_references_on_cpu():
+    """The fp64 reference helpers of tests/test_small_kernel_edges_gpu.py are plain functions: their shapes agree with the stand-in kernels of
+    tests/fake_ops.py (which the CPU engine tests run on), the compression reference floors H / sr and W / sr and gives no gradient to an uncovered
+    token, and the written-out AdamW recurrence is torch.optim.AdamW's in fp64."""
+    import fake_ops
+    import test_small_kernel_edges_gpu as e
+    B, H, W, sr, Cc = 1, 9, 7, 2, 8
+    x = e.crnd(B, H * W, Cc, seed=1).double().requires_grad_(True)
+    cw, cb, lw, lb = e.crnd(Cc, 1, sr, sr, seed=2), e.crnd(Cc, seed=3), e.crnd(Cc, seed=4), e.crnd(Cc, seed=5)
+    y = e.kv_compress_ref(x, cw, cb, lw, lb, B, H, W, sr)
+    assert y.dtype == torch.float64 and y.shape == fake_ops.kv_compress_fwd(x, 0, 0, cw, cb, lw, lb, B, H, W, Cc, sr).shape == (1, 12, 8)
+    t = x.detach()[0].view(H, W, Cc)[2:4, 4:6]                                      # compressed token (1, 2) by hand
+    conv = (t * cw.double()[:, 0].permute(1, 2, 0)).sum((0, 1)) + cb.double()
+    hand = (conv - conv.mean()) / (conv.var(unbiased=False) + 1e-5).sqrt() * lw.double() + lb.double()
+    assert rel_l2(y[0, 1 * 3 + 2], hand) < 1e-12
+    y.sum().backward()
+    cov = e.covered_tokens(H, W, sr)
+    assert int(cov.sum()) == 8 * 6 and x.grad[:, ~cov].abs().max() == 0 and (x.grad[:, cov].abs().sum(-1) > 0).all()
+    assert torch.equal(e.kv_pick_ref(x.detach(), B, H, W, sr), x.detach().view(B, H, W, Cc)[:, 0:8:2, 0:6:2].reshape(B, 12, Cc))
+    xi, w, b = e.crnd(3, 4, 10, 14, seed=1), e.crnd(16, 4, 2, 2, seed=2), e.crnd(16, seed=3)
+    pe = e.patch_embed_ref(xi, w, b, e.crnd(35, 16, seed=4))
+    assert pe.dtype == torch.float64 and tuple(pe.flatten(0, 1).shape) == tuple(fake_ops.patch_embed_fwd(xi, w, b, None).shape)
+    lin = e.crnd(3 * 5 * 7, 32, seed=1)
+    img = e.unpatchify_ref(lin, 3, 5, 7, 8)
+    assert img.shape == fake_ops.unpatchify_fwd(lin, 3, 5, 7, 8).shape and fake_ops.patchify_bwd(img, 5, 7).shape == lin.shape
+    assert img[2, 5, 2 * 3 + 1, 2 * 6 + 0] == lin[(2 * 5 + 3) * 7 + 6, (1 * 2 + 0) * 8 + 5]
+    src, alt, idx = e.crnd(6, 4, seed=1), e.crnd(2, 4, seed=2), torch.tensor([1, 2, 5], dtype=torch.int32)
+    got = e.gather_rows_ref(src, idx, 2, alt=alt, drop=torch.tensor([0, 1, 0], dtype=torch.int32))
+    assert got.shape == fake_ops.gather_rows_bf16(src, idx, 2).shape and torch.equal(got, torch.stack([src[1], alt[0], src[5]]))
+    assert torch.equal(e.gather_rows_ref(src, idx, 2), src[idx.long()])
+    p0, grads = e.crnd(1000, seed=1).double(), [e.crnd(1000, scale=0.1, seed=2).double(), e.crnd(1000, scale=0.1, seed=3).double()]
+    pr = p0.clone().requires_grad_(True)
+    opt = torch.optim.AdamW([pr], lr=2e-5, betas=(0.9, 0.999), eps=1e-10, weight_decay=3e-2)
+    for g in grads:
+        pr.grad = g.clone()
+        opt.step()
+    upd, m, v = e.adamw_ref(p0, grads, 2e-5, 0.9, 0.999, 1e-10, 3e-2)
+    assert rel_l2(upd, pr.detach() - p0) < 1e-9 and rel_l2(m, opt.state[pr]["exp_avg"]) < 1e-14 and rel_l2(v, opt.state[pr]["exp_avg_sq"]) < 1e-14
