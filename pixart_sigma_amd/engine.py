@@ -5,7 +5,7 @@ libpixart_hip.so (ops.py -> C ABI).  Mirrors the dataflow of PixArtMS.forward / 
 
   block l:  x_in  = x2[l-1] + gate_mlp[l-1]*u3[l-1] ; xn1 = LN(x_in)(1+scale_msa)+shift_msa      (ln_mod_fwd, 1 pass)
             qkv   = xn1 Wqkv^T + b                                                                (gemm NT)
-            a     = softmax(q k^T/sqrt(72)) v          [k,v optionally KV-compressed]             (attn_fwd)
+            a     = softmax(q k^T/sqrt(hd)) v          [k,v optionally KV-compressed]             (attn_fwd)
             u1    = a Wproj^T + b                                                                 (gemm NT)
             x1    = x_in + gate_msa*u1 ; x1b = bf16(x1)                                           (ln_mod_fwd, no LN)
             qc    = x1b Wq^T + b ; kvc = y Wkv^T + b ; c = varlen-attn(qc, kvc) ; u2 = c Wcp^T+b  (gemm, attn_fwd, gemm)
@@ -17,8 +17,10 @@ The residual stream, LayerNorm statistics, softmax and all accumulators are fp32
 stored branch activations are bf16 (DESIGN.md "Numerics").  Backward is hand-sequenced (no autograd inside): weight
 gradients are accumulated straight into the flat fp32 gradient buffer (ParamStore.grad).
 """
-import math
+import collections
+import dataclasses
 import os
+import typing
 import weakref
 
 import numpy as np
@@ -66,7 +68,7 @@ class ParamStore:
         for name, p in named_params:
             self.names.append(name)
             self.offset[name], self.shape[name], self.numel[name] = off, tuple(p.shape), p.numel()
-            end = off + (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+            end = self._end(name)
             if group_of is not None:
                 gname = group_of(name)
                 if gname in self.groups:
@@ -90,6 +92,10 @@ class ParamStore:
             p.data = v
             p.grad = self.view(self.grad, name)
 
+    def _end(self, name):
+        """End of the parameter's aligned slot = offset of the one behind it."""
+        return self.offset[name] + (self.numel[name] + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+
     def view(self, flat, name):
         o = self.offset[name]
         return flat[o:o + self.numel[name]].view(self.shape[name])
@@ -107,17 +113,14 @@ class ParamStore:
         """[start, end) element range of all parameters whose name starts with prefix (contiguous by construction)."""
         idx = [i for i, n in enumerate(self.names) if n.startswith(prefix)]
         assert idx and idx == list(range(idx[0], idx[-1] + 1)), prefix
-        last = self.names[idx[-1]]
-        end = self.offset[last] + (self.numel[last] + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        return self.offset[self.names[idx[0]]], end
+        return self.offset[self.names[idx[0]]], self._end(self.names[idx[-1]])
 
     def bias_range(self, prefix):
         """[start, end) of the contiguous run of '*.bias' parameters under `prefix` (the model orders a block's weights first,
         then its biases, so that fused bias-gradient partials can be folded into the gradient buffer with one launch)."""
         idx = [i for i, n in enumerate(self.names) if n.startswith(prefix) and n.endswith(".bias")]
         assert idx and idx == list(range(idx[0], idx[-1] + 1)), f"biases under {prefix} are not contiguous in the flat store"
-        last = self.names[idx[-1]]
-        return self.offset[self.names[idx[0]]], self.offset[last] + (self.numel[last] + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        return self.offset[self.names[idx[0]]], self._end(self.names[idx[-1]])
 
     def owns(self, p, name):
         return p.data_ptr() == self.master.data_ptr() + 4 * self.offset[name] and p.device == self.master.device
@@ -168,9 +171,37 @@ class ParamStore:
         return True
 
 
-def _splitk(M, N, K):
-    tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    return max(1, min((640 + tiles - 1) // tiles, max(1, K // 512)))
+@dataclasses.dataclass
+class StepCtx:
+    """What every block of one forward / backward reads: geometry, the modulation tensor (L, B, 6, D), the text-length index tensors of the varlen
+    cross-attention and the packed caption rows `ye`.  Built by Engine.step_ctx.  kvc: inference only, the per-block cross-attention K / V list of
+    Engine._text_cache.  dmod / dye: the backward's accumulators for d(mod) and d(ye)."""
+    B: int
+    N: int
+    hw: tuple
+    mod: torch.Tensor
+    kv_len: torch.Tensor
+    kv_start: torch.Tensor
+    max_len: int
+    lens_host: typing.Optional[tuple]
+    need_grad_aux: bool = True         # False: no backward reads this forward's GELU' (inference, the discarded forward of a checkpointed step)
+    ye: typing.Optional[torch.Tensor] = None
+    kvc: typing.Optional[list] = None
+    dmod: typing.Optional[torch.Tensor] = None
+    dye: typing.Optional[torch.Tensor] = None
+
+
+# Where a block's self-attention reads its keys / values and how their gradients get back into dqkv (Engine._self_kv).  k, v, Nk, sk: what attention is
+# handed (sk = the key / value strides).  bwd: 'direct' - dK / dV are dqkv's own k, v column blocks; 'strided' - the same, on every sr-th token;
+# 'compress' / 'pick' - k, v are compressed buffers whose gradients go through kv_compress_bwd / kv_pick into dqkv.  zero_dqkv: that path leaves rows
+# of dqkv unwritten, so it must start zeroed.
+SelfKV = collections.namedtuple("SelfKV", "k v Nk sk bwd zero_dqkv")
+
+# What block_fwd keeps for block_bwd (skv: the block's SelfKV; qkn: the q_norm / k_norm outputs).  save='ckpt' keeps x_in alone and _recompute makes the rest again.
+BlockSaved = collections.namedtuple("BlockSaved", "x_in mean1 rstd1 xn1 qkv a lse u1 x1b qc kvc cr lse_c x2 mean2 rstd2 xn2 hpre h u3 skv qkn", defaults=(None,) * 21)
+
+# What Engine.forward keeps for Engine.backward.  blocks: one BlockSaved per block, released as the backward passes it.
+Saved = collections.namedtuple("Saved", "ctx blocks cap x x3 meanf rstdf xnf fin_mod mode")
 
 
 class Engine:
@@ -192,7 +223,8 @@ class Engine:
         # multiply per score less in the dK/dV kernel, and the fp16 forward's folded first product loses its second rounding of q.  The backward is
         # untouched: dq comes out with respect to the unscaled queries and the dX / dW GEMMs read the true weights.  Off under qk_norm (the LayerNorm behind
         # the projection would normalise the factor away) and with PXA_Q_PRESCALE=0 (A/B).
-        self.prescale = (not cfg.get("qk_norm")) and os.environ.get("PXA_Q_PRESCALE", "1") != "0" and cfg["hidden_size"] // cfg["num_heads"] == 72
+        self.head_dim = cfg["hidden_size"] // cfg["num_heads"]
+        self.prescale = (not cfg.get("qk_norm")) and os.environ.get("PXA_Q_PRESCALE", "1") != "0" and self.head_dim == 72
         # The copy lives in ONE pair of buffers per engine, allocated here and rewritten in place whenever the shadow weights change (ParamStore.bump):
         # a HIP graph captured over the forward (DPM_Solver.sample_graphed) bakes these addresses exactly as it bakes the shadow's, and replays after an
         # optimizer step / weight load read current values (the per-generation allocation it replaces left such a graph reading a freed block,
@@ -212,6 +244,22 @@ class Engine:
             self._pos_cache[key] = torch.from_numpy(tab).to(F32).to(self.S.device).contiguous()
         return self._pos_cache[key]
 
+    def step_ctx(self, B, N, hw, mod, lens):
+        lk = tuple(int(v) for v in lens)
+        if lk not in self._len_cache:                        # per-sample text lengths -> device index tensors, uploaded once per distinct set
+            if len(self._len_cache) > 64:
+                self._len_cache.clear()
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+            self._len_cache[lk] = (torch.tensor(lens, dtype=torch.int32, device=mod.device), torch.from_numpy(starts).to(mod.device))
+        kv_len, kv_start = self._len_cache[lk]
+        return StepCtx(B, N, hw, mod, kv_len, kv_start, int(max(lens)), lk)
+
+    def _cross_strides(self, N):
+        """(batch, token, head) element strides of q, k, v, o of the cross-attention; the first three are its backward's dstrides.  k / v: column halves of
+        the packed text rows (found through kv_start)."""
+        D, hd = self.cfg["hidden_size"], self.head_dim
+        return ((N * D, D, hd), (0, 2 * D, hd), (0, 2 * D, hd), (N * D, D, hd))
+
     # Item order of the token GEMMs (round 5, pxa_gemm_args.items_descending).  Every row kernel and attention kernel sweeps the token rows upwards, so the rows it
     # wrote LAST are the ones still in the 256 MB Infinity Cache when the next GEMM starts: that GEMM walks its tiles downwards, and its own output then ends with the
     # first rows - fresh for the ascending consumer behind it.  The second GEMM of a GEMM -> GEMM pair (fc2 behind fc1; fc1's dX behind fc2's dX) follows its
@@ -226,7 +274,6 @@ class Engine:
     def _lin_bwd(self, dy, x, name, need_dx=True, dx_kw=None, bias_done=False):
         """dW += dy^T x ; db += colsum(dy) (unless the kernel that produced dy already accumulated it) ; returns dx = dy W (bf16)."""
         S = self.S
-        M, N = S.shape[name + ".weight"]
         # (order measured: the weight gradient FIRST - its pass over dy leaves dy in the Infinity Cache for the dX GEMM; dX first is 1.6 ms per step slower,
         # profiles/r5_20_step_ab_dx_first.txt)
         ops.gemm(dy, x, TN, out_f32=S.g(name + ".weight"), accumulate=True, split_k=0)
@@ -254,10 +301,6 @@ class Engine:
             ops.scale_copy(S.master[offb[i]:], st if n > 1 else 0, n, D, 3 * D, ops.Q_PRESCALE, out_f32=b[i:i + n])
             i += n
 
-    def _qkv_prescaled(self, l):
-        """(weight (3D, D) in the operand type, bias (3D,) fp32) of block l with the q rows times scale * log2 e: views of the engine's persistent copy."""
-        return self._qs[0][l], self._qs[1][l]
-
     # ------------------------------------------------------------------ caption branch
     def caption_fwd(self, y, row_idx, L, drop, y_null):
         """y (B*L, 4096) fp32 -> packed y_emb (Ltot, D) bf16  (CaptionEmbedder, PixArt_blocks.py:400-407 after masked_select).
@@ -277,94 +320,93 @@ class Engine:
         self._lin_bwd(dh, yb, "y_embedder.y_proj.fc1", need_dx=False)
 
     # ------------------------------------------------------------------ block
-    def block_fwd(self, l, x_prev, u_prev, gate_prev, ctx):
-        """Returns (x2, u3, saved).  x_prev/u_prev/gate_prev: residual, pending gated branch of the previous block."""
+    def _self_kv(self, l, qkv, ctx):
+        """The one place that knows where block l's self-attention reads its keys / values: qkv's own column blocks, or one of the KV-compression modes
+        (PixArt_blocks.py:97-115), whose forward kernels are launched here."""
         S, c = self.S, self.cfg
-        B, N, D, H = ctx["B"], ctx["N"], c["hidden_size"], c["num_heads"]
+        B, N, D = ctx.B, ctx.N, c["hidden_size"]
+        p = f"blocks.{l}.attn."
+        k, v, bs, ts = qkv[:, D:2 * D], qkv[:, 2 * D:], N * 3 * D, 3 * D
+        sr = c["kv_scale_factor"] if l in c["kv_layers"] else 1
+        if sr == 1:
+            return SelfKV(k, v, N, (bs, ts, self.head_dim), "direct", False)
+        hh, ww = ctx.hw
+        if c["kv_sampling"] == "conv":
+            cw, cb, lw, lb = S.f(p + "sr.weight"), S.f(p + "sr.bias"), S.f(p + "norm.weight"), S.f(p + "norm.bias")
+            kc = ops.kv_compress_fwd(k, bs, ts, cw, cb, lw, lb, B, hh, ww, D, sr)
+            vc = ops.kv_compress_fwd(v, bs, ts, cw, cb, lw, lb, B, hh, ww, D, sr)
+            bwd, zero = "compress", not (hh % sr == 0 and ww % sr == 0)      # covered: every token lies in a window, kv_compress_bwd writes all of dqkv's k, v
+        elif c["kv_sampling"] == "uniform_every":          # strided keys: gradients land on the picked tokens, the rest stay zero
+            return SelfKV(k, v, (N + sr - 1) // sr, (bs, ts * sr, self.head_dim), "strided", True)
+        elif c["kv_sampling"] in ("uniform", "ave"):      # 'ave' = nearest interpolation = the same strided pick (PixArt_blocks.py:110-115)
+            kc = torch.empty((B, (hh // sr) * (ww // sr), D), dtype=BF16, device=qkv.device)
+            vc = torch.empty_like(kc)
+            ops.kv_pick(k, kc, bs, ts, B, hh, ww, D, sr)
+            ops.kv_pick(v, vc, bs, ts, B, hh, ww, D, sr)
+            bwd, zero = "pick", True
+        else:
+            raise ValueError(f"unknown kv sampling mode {c['kv_sampling']!r}")
+        Nk = kc.shape[1]
+        return SelfKV(kc, vc, Nk, (Nk * D, D, self.head_dim), bwd, zero)
+
+    def block_fwd(self, l, x_prev, u_prev, gate_prev, ctx):
+        """Returns (x2, u3, gate_mlp, saved).  x_prev/u_prev/gate_prev: residual, pending gated branch of the previous block."""
+        S, c = self.S, self.cfg
+        B, N, D, H = ctx.B, ctx.N, c["hidden_size"], c["num_heads"]
         p = f"blocks.{l}."
-        mod = ctx["mod"][l]                                   # (B, 6, D) fp32 view
+        mod = ctx.mod[l]                                      # (B, 6, D) fp32 view
         sm, scm, gm, sl, scl, gl = (mod[:, i] for i in range(6))
         st = 6 * D
         r = ops.ln_mod_fwd(x_prev, sm, scm, st, u=u_prev, gate=gate_prev, gate_stride=st, rows_per_batch=N, want_stats=True)
         x_in, xn1, mean1, rstd1 = r["x"], r["xn"], r["mean"], r["rstd"]
         pre = dict(q_prescaled=True) if self.prescale else {}
-        if self.prescale:
-            wq, bq = self._qkv_prescaled(l)
-            qkv = ops.gemm(xn1, wq, NT, bias=bq, descending=True)
+        if self.prescale:           # block l's views of the engine's persistent copy: weight (3D, D), bias (3D,) with the q rows times scale * log2 e
+            qkv = ops.gemm(xn1, self._qs[0][l], NT, bias=self._qs[1][l], descending=True)
         else:
             qkv = self._lin(xn1, p + "attn.qkv")
         qkn = None
         if c.get("qk_norm"):        # q_norm / k_norm on the full-resolution q, k column blocks, in place (PixArt_blocks.py:133-134)
             qkn = (ops.ln_affine_fwd(qkv[:, :D], S.f(p + "attn.q_norm.weight"), S.f(p + "attn.q_norm.bias")),
                    ops.ln_affine_fwd(qkv[:, D:2 * D], S.f(p + "attn.k_norm.weight"), S.f(p + "attn.k_norm.bias")))
-        sr = c["kv_scale_factor"] if l in c["kv_layers"] else 1
         a = torch.empty((B * N, D), dtype=BF16, device=qkv.device)
         lse = torch.empty((B, H, N), dtype=F32, device=qkv.device)
-        s3 = (N * 3 * D, 3 * D, 72)
-        kc = vc = None
-        if sr > 1:
-            hh, ww = ctx["hw"]
-            if c["kv_sampling"] == "conv":
-                cw, cb = S.f(p + "attn.sr.weight"), S.f(p + "attn.sr.bias")
-                lw, lb = S.f(p + "attn.norm.weight"), S.f(p + "attn.norm.bias")
-                kc = ops.kv_compress_fwd(qkv[:, D:2 * D], N * 3 * D, 3 * D, cw, cb, lw, lb, B, hh, ww, D, sr)
-                vc = ops.kv_compress_fwd(qkv[:, 2 * D:], N * 3 * D, 3 * D, cw, cb, lw, lb, B, hh, ww, D, sr)
-                Nk = kc.shape[1]
-                sk = (Nk * D, D, 72)
-                ops.attention_fwd(qkv[:, :D], kc, vc, a, lse, B, H, N, Nk, (s3, sk, sk, (N * D, D, 72)), **pre)
-            elif c["kv_sampling"] == "uniform_every":
-                Nk = (N + sr - 1) // sr
-                sk = (N * 3 * D, 3 * D * sr, 72)
-                ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, lse, B, H, N, Nk, (s3, sk, sk, (N * D, D, 72)), **pre)
-            elif c["kv_sampling"] in ("uniform", "ave"):      # 'ave' = nearest interpolation = the same strided pick (PixArt_blocks.py:110-115)
-                Nk = (hh // sr) * (ww // sr)
-                kc = torch.empty((B, Nk, D), dtype=BF16, device=qkv.device)
-                vc = torch.empty((B, Nk, D), dtype=BF16, device=qkv.device)
-                ops.kv_pick(qkv[:, D:2 * D], kc, N * 3 * D, 3 * D, B, hh, ww, D, sr)
-                ops.kv_pick(qkv[:, 2 * D:], vc, N * 3 * D, 3 * D, B, hh, ww, D, sr)
-                sk = (Nk * D, D, 72)
-                ops.attention_fwd(qkv[:, :D], kc, vc, a, lse, B, H, N, Nk, (s3, sk, sk, (N * D, D, 72)), **pre)
-            else:
-                raise ValueError(f"unknown kv sampling mode {c['kv_sampling']!r}")
-        else:
-            ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, lse, B, H, N, N, (s3, s3, s3, (N * D, D, 72)), **pre)
+        skv = self._self_kv(l, qkv, ctx)
+        ops.attention_fwd(qkv[:, :D], skv.k, skv.v, a, lse, B, H, N, skv.Nk, ((N * 3 * D, 3 * D, self.head_dim), skv.sk, skv.sk, (N * D, D, self.head_dim)), **pre)
         u1 = self._lin(a, p + "attn.proj")
         r = ops.ln_mod_fwd(x_in, u=u1, gate=gm, gate_stride=st, want_xn=False, want_xb=True, rows_per_batch=N)
         x1, x1b = r["x"], r["xb"]
         qc = self._lin(x1b, p + "cross_attn.q_linear")
-        ye = ctx["ye"]
-        kvc = ctx["kvc"][l] if ctx.get("kvc") is not None else None      # inference: constant over the sampler's steps (Engine._text_cache)
+        kvc = ctx.kvc[l] if ctx.kvc is not None else None      # inference: constant over the sampler's steps (Engine._text_cache)
         if kvc is None:
-            kvc = self._lin(ye, p + "cross_attn.kv_linear")
-            if ctx.get("kvc") is not None:
-                ctx["kvc"][l] = kvc
+            kvc = self._lin(ctx.ye, p + "cross_attn.kv_linear")
+            if ctx.kvc is not None:
+                ctx.kvc[l] = kvc
         cr = torch.empty((B * N, D), dtype=BF16, device=qkv.device)
         lse_c = torch.empty((B, H, N), dtype=F32, device=qkv.device)
-        sc_str = ((N * D, D, 72), (0, 2 * D, 72), (0, 2 * D, 72), (N * D, D, 72))
-        ops.attention_fwd(qc, kvc[:, :D], kvc[:, D:], cr, lse_c, B, H, N, ctx["max_len"], sc_str,
-                          kv_start=ctx["kv_start"], kv_len=ctx["kv_len"], max_kv_len=ctx["max_len"], kv_len_host=ctx.get("lens_host"))
+        ops.attention_fwd(qc, kvc[:, :D], kvc[:, D:], cr, lse_c, B, H, N, ctx.max_len, self._cross_strides(N),
+                          kv_start=ctx.kv_start, kv_len=ctx.kv_len, max_kv_len=ctx.max_len, kv_len_host=ctx.lens_host)
         u2 = self._lin(cr, p + "cross_attn.proj")
         r = ops.ln_mod_fwd(x1, sl, scl, st, u=u2, x_out=x1, rows_per_batch=N, want_stats=True)
         x2, xn2, mean2, rstd2 = r["x"], r["xn"], r["mean"], r["rstd"]
-        if ctx.get("need_grad_aux", True):
+        if ctx.need_grad_aux:
             hpre = torch.empty((B * N, S.shape[p + "mlp.fc1.weight"][0]), dtype=BF16, device=qkv.device)
             h = self._lin(xn2, p + "mlp.fc1", act=ops.ACT_GELU_SAVE_GRAD, out2=hpre)   # hpre holds GELU'(pre-activation), bf16
         else:                                      # inference / the discarded forward of a checkpointed step: no backward reads GELU' - one output, half the
             hpre = None                            # epilogue's transcendentals and stores
             h = self._lin(xn2, p + "mlp.fc1", act=ops.ACT_GELU)
         u3 = self._lin(h, p + "mlp.fc2")
-        saved = dict(x_in=x_in, mean1=mean1, rstd1=rstd1, xn1=xn1, qkv=qkv, a=a, lse=lse, u1=u1, x1b=x1b, qc=qc, kvc=kvc,
-                     cr=cr, lse_c=lse_c, x2=x2, mean2=mean2, rstd2=rstd2, xn2=xn2, hpre=hpre, h=h, u3=u3, kc=kc, vc=vc, sr=sr, qkn=qkn)
+        saved = BlockSaved(x_in=x_in, mean1=mean1, rstd1=rstd1, xn1=xn1, qkv=qkv, a=a, lse=lse, u1=u1, x1b=x1b, qc=qc, kvc=kvc,
+                           cr=cr, lse_c=lse_c, x2=x2, mean2=mean2, rstd2=rstd2, xn2=xn2, hpre=hpre, h=h, u3=u3, skv=skv, qkn=qkn)
         return x2, u3, gl, saved
 
     def block_bwd(self, l, G, sv, ctx):
         """G: fp32 (R, D) gradient w.r.t. this block's output residual x3 = x2 + gate_mlp*u3; overwritten with the
         gradient w.r.t. x_in.  Accumulates parameter gradients, d(mod) and d(y_emb)."""
         S, c = self.S, self.cfg
-        B, N, D, H = ctx["B"], ctx["N"], c["hidden_size"], c["num_heads"]
+        B, N, D, H = ctx.B, ctx.N, c["hidden_size"], c["num_heads"]
         R = B * N
         p = f"blocks.{l}."
-        mod, dmod = ctx["mod"][l], ctx["dmod"][l]
+        mod, dmod = ctx.mod[l], ctx.dmod[l]
         st = 6 * D
         dev = G.device
         # bias gradients ride along with the kernels that produce the output gradients (no separate column-sum passes); they add
@@ -377,77 +419,84 @@ class Engine:
             return part[:, o + lo:o + (S.numel[p + name] if hi is None else hi)]
         # ---- MLP branch: x3 = x2 + gate_mlp * u3
         du = torch.empty((R, D), dtype=BF16, device=dev)
-        ops.gate_bwd(G, u=sv["u3"], gate=mod[:, 5], mod_stride=st, du=du, dgate=dmod[:, 5], dmod_stride=st, rows_per_batch=N,
+        ops.gate_bwd(G, u=sv.u3, gate=mod[:, 5], mod_stride=st, du=du, dgate=dmod[:, 5], dmod_stride=st, rows_per_batch=N,
                      dbias=pb("mlp.fc2.bias"))
-        dh = self._lin_bwd(du, sv["h"], p + "mlp.fc2", dx_kw=dict(act=ops.ACT_MUL_AUX, aux=sv["hpre"], colsum=pb("mlp.fc1.bias")), bias_done=True)
-        dxn = self._lin_bwd(dh, sv["xn2"], p + "mlp.fc1", bias_done=True)
+        dh = self._lin_bwd(du, sv.h, p + "mlp.fc2", dx_kw=dict(act=ops.ACT_MUL_AUX, aux=sv.hpre, colsum=pb("mlp.fc1.bias")), bias_done=True)
+        dxn = self._lin_bwd(dh, sv.xn2, p + "mlp.fc1", bias_done=True)
         del dh
         # ---- cross attention: x2 = x1 + u2 (no gate, no norm): du2 = bf16(G2) comes out of the LN backward pass itself
         # (round 5: cross_attn.proj's bias gradient = column sums of G2 ride in this pass; PXA_FUSED_CPROJ_BIAS=0: the separate colsum pass, A/B)
         fused_cb = os.environ.get("PXA_FUSED_CPROJ_BIAS", "1") != "0"
-        ops.ln_mod_bwd(dxn, sv["x2"], sv["mean2"], sv["rstd2"], mod[:, 4], st, G, G, dmod[:, 3], dmod[:, 4], st, N, dx_bf16=du,
+        ops.ln_mod_bwd(dxn, sv.x2, sv.mean2, sv.rstd2, mod[:, 4], st, G, G, dmod[:, 3], dmod[:, 4], st, N, dx_bf16=du,
                        dbias=pb("cross_attn.proj.bias") if fused_cb else None)
-        dc = self._lin_bwd(du, sv["cr"], p + "cross_attn.proj", bias_done=fused_cb)
+        dc = self._lin_bwd(du, sv.cr, p + "cross_attn.proj", bias_done=fused_cb)
         dqc = torch.empty((R, D), dtype=BF16, device=dev)
-        dkvc = torch.empty_like(sv["kvc"])
+        dkvc = torch.empty_like(sv.kvc)
         delta = torch.empty((B, H, N), dtype=F32, device=dev)
-        sc_str = ((N * D, D, 72), (0, 2 * D, 72), (0, 2 * D, 72), (N * D, D, 72))
-        ops.attention_bwd(sv["qc"], sv["kvc"][:, :D], sv["kvc"][:, D:], sv["cr"], dc, sv["lse_c"], delta, dqc, dkvc[:, :D], dkvc[:, D:],
-                          B, H, N, ctx["max_len"], sc_str, ((N * D, D, 72), (0, 2 * D, 72), (0, 2 * D, 72)),
-                          kv_start=ctx["kv_start"], kv_len=ctx["kv_len"], max_kv_len=ctx["max_len"], kv_len_host=ctx.get("lens_host"))
-        gq = self._lin_bwd(dqc, sv["x1b"], p + "cross_attn.q_linear")
-        # 4,800 text rows fill 95 of 256 CUs with 256 x 256 tiles: split_k = 0 lets the library's (tile, split) model choose (128 x 128 here: 72 -> 47 us)
-        self._lin_bwd(dkvc, ctx["ye"], p + "cross_attn.kv_linear", dx_kw=dict(out_f32=ctx["dye"], accumulate=True, split_k=0))
+        sc_str = self._cross_strides(N)
+        ops.attention_bwd(sv.qc, sv.kvc[:, :D], sv.kvc[:, D:], sv.cr, dc, sv.lse_c, delta, dqc, dkvc[:, :D], dkvc[:, D:],
+                          B, H, N, ctx.max_len, sc_str, sc_str[:3],
+                          kv_start=ctx.kv_start, kv_len=ctx.kv_len, max_kv_len=ctx.max_len, kv_len_host=ctx.lens_host)
+        gq = self._lin_bwd(dqc, sv.x1b, p + "cross_attn.q_linear")
+        # 4,800 text rows fill 95 of 256 CUs with 256 x 256 tiles: split_k = 0 lets the library's (tile, split) model choose (128 x 128 here: 72us -> 47us)
+        self._lin_bwd(dkvc, ctx.ye, p + "cross_attn.kv_linear", dx_kw=dict(out_f32=ctx.dye, accumulate=True, split_k=0))
         # ---- self attention: x1 = x_in + gate_msa * u1 ; G1 = G + gq
-        ops.gate_bwd(G, add=gq, u=sv["u1"], gate=mod[:, 2], mod_stride=st, dx_out=G, du=du, dgate=dmod[:, 2], dmod_stride=st, rows_per_batch=N,
+        ops.gate_bwd(G, add=gq, u=sv.u1, gate=mod[:, 2], mod_stride=st, dx_out=G, du=du, dgate=dmod[:, 2], dmod_stride=st, rows_per_batch=N,
                      dbias=pb("attn.proj.bias"))
-        da = self._lin_bwd(du, sv["a"], p + "attn.proj", bias_done=True)
-        qkv = sv["qkv"]
-        s3 = (N * 3 * D, 3 * D, 72)
-        so = (N * D, D, 72)
-        sr = sv["sr"]
+        da = self._lin_bwd(du, sv.a, p + "attn.proj", bias_done=True)
+        qkv, skv = sv.qkv, sv.skv
+        s3 = (N * 3 * D, 3 * D, self.head_dim)
         pre = dict(q_prescaled=True) if self.prescale else {}
-        if sr == 1:
-            dqkv = torch.empty_like(qkv)
-            ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sv["a"], da, sv["lse"], delta, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                              B, H, N, N, (s3, s3, s3, so), (s3, s3, s3), **pre)
-        elif c["kv_sampling"] == "uniform_every":          # strided keys: gradients land on the picked tokens, the rest stay zero
-            dqkv = torch.zeros_like(qkv)
-            Nk = (N + sr - 1) // sr
-            sk = (N * 3 * D, 3 * D * sr, 72)
-            ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sv["a"], da, sv["lse"], delta, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                              B, H, N, Nk, (s3, sk, sk, so), (s3, sk, sk), **pre)
+        dqkv = torch.zeros_like(qkv) if skv.zero_dqkv else torch.empty_like(qkv)
+        if skv.bwd in ("direct", "strided"):
+            dk, dv = dqkv[:, D:2 * D], dqkv[:, 2 * D:]
         else:                                               # compressed K/V buffers: attention backward, then the compression's backward
-            hh, ww = ctx["hw"]
-            kc, vc = sv["kc"], sv["vc"]
-            Nk = kc.shape[1]
-            sk = (Nk * D, D, 72)
-            covered = (hh % sr == 0) and (ww % sr == 0) and c["kv_sampling"] == "conv"
-            dqkv = torch.empty_like(qkv) if covered else torch.zeros_like(qkv)
-            dkc, dvc = torch.empty_like(kc), torch.empty_like(vc)
-            ops.attention_bwd(qkv[:, :D], kc, vc, sv["a"], da, sv["lse"], delta, dqkv[:, :D], dkc, dvc, B, H, N, Nk, (s3, sk, sk, so), (s3, sk, sk), **pre)
-            if c["kv_sampling"] == "conv":
-                cw, cb, lw = S.f(p + "attn.sr.weight"), S.f(p + "attn.sr.bias"), S.f(p + "attn.norm.weight")
-                gcw, gcb = S.g(p + "attn.sr.weight"), S.g(p + "attn.sr.bias")
-                glw, glb = S.g(p + "attn.norm.weight"), S.g(p + "attn.norm.bias")
-                for dyc, lo in ((dkc, D), (dvc, 2 * D)):   # the same sr / norm parameters process K and V (PixArt_blocks.py:138-139)
-                    ops.kv_compress_bwd(dyc, qkv[:, lo:lo + D], N * 3 * D, 3 * D, cw, cb, lw, dqkv[:, lo:lo + D], N * 3 * D, 3 * D,
-                                        gcw, gcb, glw, glb, B, hh, ww, D, sr)
-            else:
-                ops.kv_pick(dkc, dqkv[:, D:2 * D], N * 3 * D, 3 * D, B, hh, ww, D, sr, backward=True)
-                ops.kv_pick(dvc, dqkv[:, 2 * D:], N * 3 * D, 3 * D, B, hh, ww, D, sr, backward=True)
-        if sv.get("qkn") is not None:                        # back through q_norm / k_norm: dqkv's q, k blocks become d(raw q), d(raw k)
-            (qs, qm, qr), (ks_, km, kr) = sv["qkn"]
+            dk, dv = torch.empty_like(skv.k), torch.empty_like(skv.v)
+        ops.attention_bwd(qkv[:, :D], skv.k, skv.v, sv.a, da, sv.lse, delta, dqkv[:, :D], dk, dv,
+                          B, H, N, skv.Nk, (s3, skv.sk, skv.sk, (N * D, D, self.head_dim)), (s3, skv.sk, skv.sk), **pre)
+        if skv.bwd == "compress":
+            (hh, ww), sr = ctx.hw, c["kv_scale_factor"]
+            cw, cb, lw = S.f(p + "attn.sr.weight"), S.f(p + "attn.sr.bias"), S.f(p + "attn.norm.weight")
+            gcw, gcb = S.g(p + "attn.sr.weight"), S.g(p + "attn.sr.bias")
+            glw, glb = S.g(p + "attn.norm.weight"), S.g(p + "attn.norm.bias")
+            for dyc, lo in ((dk, D), (dv, 2 * D)):     # the same sr / norm parameters process K and V (PixArt_blocks.py:138-139)
+                ops.kv_compress_bwd(dyc, qkv[:, lo:lo + D], N * 3 * D, 3 * D, cw, cb, lw, dqkv[:, lo:lo + D], N * 3 * D, 3 * D,
+                                    gcw, gcb, glw, glb, B, hh, ww, D, sr)
+        elif skv.bwd == "pick":
+            (hh, ww), sr = ctx.hw, c["kv_scale_factor"]
+            ops.kv_pick(dk, dqkv[:, D:2 * D], N * 3 * D, 3 * D, B, hh, ww, D, sr, backward=True)
+            ops.kv_pick(dv, dqkv[:, 2 * D:], N * 3 * D, 3 * D, B, hh, ww, D, sr, backward=True)
+        if sv.qkn is not None:                               # back through q_norm / k_norm: dqkv's q, k blocks become d(raw q), d(raw k)
+            (qs, qm, qr), (ks_, km, kr) = sv.qkn
             ops.ln_affine_bwd(dqkv[:, :D], qs, qm, qr, S.f(p + "attn.q_norm.weight"), S.g(p + "attn.q_norm.weight"), S.g(p + "attn.q_norm.bias"))
             ops.ln_affine_bwd(dqkv[:, D:2 * D], ks_, km, kr, S.f(p + "attn.k_norm.weight"), S.g(p + "attn.k_norm.weight"), S.g(p + "attn.k_norm.bias"))
         # the attention kernels can also emit the q/k/v bias-gradient sums (pxa_attn_args.d*_colsum), but the cross-lane row
         # reductions cost them more (~0.5 ms/block) than one streaming column-sum pass over dqkv (~0.2 ms/block): measured, not used
-        dxn = self._lin_bwd(dqkv, sv["xn1"], p + "attn.qkv")
-        ops.ln_mod_bwd(dxn, sv["x_in"], sv["mean1"], sv["rstd1"], mod[:, 1], st, G, G, dmod[:, 0], dmod[:, 1], st, N)
+        dxn = self._lin_bwd(dqkv, sv.xn1, p + "attn.qkv")
+        ops.ln_mod_bwd(dxn, sv.x_in, sv.mean1, sv.rstd1, mod[:, 1], st, G, G, dmod[:, 0], dmod[:, 1], st, N)
         ops.colsum_reduce(part, S.grad[bs:be])
         if self.grad_ready_hook:
             self.grad_ready_hook(f"blocks.{l}")
         return G
+
+    def block_standalone_fwd(self, x, y, mod, lens, hw):
+        """One block outside the model (PixArtMSBlock.forward): x (B*N, D) fp32, y the packed text rows (.., D), mod (1, B, 6, D) fp32.
+        Returns (x2 + gate_mlp * u3 as (B*N, D) fp32, what block_standalone_bwd needs)."""
+        B, D = mod.shape[1], mod.shape[3]
+        N = x.shape[0] // B
+        ctx = self.step_ctx(B, N, hw, mod, lens)
+        ctx.lens_host = None                       # as before the one step_ctx: no host copy of the lengths goes to the attention wrappers from here
+        ctx.ye = y.reshape(-1, D).to(BF16).contiguous()
+        x2, u3, gl, sv = self.block_fwd(0, x, None, None, ctx)
+        r = ops.ln_mod_fwd(x2, u=u3, gate=gl, gate_stride=6 * D, want_xn=False, rows_per_batch=N)    # the pending gated MLP branch: inside the model the next block's first pass
+        return r["x"], (ctx, sv)
+
+    def block_standalone_bwd(self, G, saved):
+        """G (B*N, D) fp32, overwritten -> (d x, d mod (B, 6, D), d y (Ltot, D) fp32); parameter gradients go to the flat buffer."""
+        ctx, sv = saved
+        ctx.dmod = torch.zeros_like(ctx.mod)
+        ctx.dye = torch.zeros(ctx.ye.shape, dtype=F32, device=G.device)
+        return self.block_bwd(0, G, sv, ctx), ctx.dmod[0], ctx.dye
 
     # ------------------------------------------------------------------ whole core
     def forward(self, x, y, mod, fin_mod, row_idx, lens, drop, save, y_null=None):
@@ -456,15 +505,8 @@ class Engine:
         B, _, Hl, Wl = x.shape
         h, w = Hl // 2, Wl // 2
         N, D, depth = h * w, c["hidden_size"], c["depth"]
-        dev = x.device
-        lk = tuple(int(v) for v in lens)
-        if lk not in self._len_cache:                        # per-sample text lengths -> device index tensors, uploaded once per distinct set
-            if len(self._len_cache) > 64:
-                self._len_cache.clear()
-            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
-            self._len_cache[lk] = (torch.tensor(lens, dtype=torch.int32, device=dev), torch.from_numpy(starts).to(dev))
-        kv_len, kv_start = self._len_cache[lk]
-        ctx = dict(B=B, N=N, hw=(h, w), mod=mod, kv_len=kv_len, kv_start=kv_start, max_len=int(max(lens)), lens_host=lk, need_grad_aux=(save == "all"))
+        ctx = self.step_ctx(B, N, (h, w), mod, lens)
+        ctx.need_grad_aux = save == "all"
         L = y.shape[0] // B
         tkey = None
         if save or torch.is_grad_enabled():
@@ -472,58 +514,57 @@ class Engine:
         elif _capturing() or os.environ.get("PXA_TEXT_CACHE", "1") == "0":
             pass                                  # a captured graph must own every buffer it reads: no cache inside sample_graphed's capture
         else:
-            tkey = (S.generation, y.data_ptr(), y._version, tuple(y.shape), lk, None if drop is None else (drop.data_ptr(), drop._version),
+            tkey = (S.generation, y.data_ptr(), y._version, tuple(y.shape), ctx.lens_host, None if drop is None else (drop.data_ptr(), drop._version),
                     None if y_null is None else (y_null.data_ptr(), y_null._version), row_idx.data_ptr())
         if tkey is not None and self._text_cache is not None and self._text_cache["key"] == tkey:
-            ye, cap_saved = self._text_cache["ye"], None
-            ctx["kvc"] = self._text_cache["kvc"]
+            ctx.ye, cap_saved = self._text_cache["ye"], None
+            ctx.kvc = self._text_cache["kvc"]
         else:
-            ye, cap_saved = self.caption_fwd(y, row_idx, L, drop, y_null)
+            ctx.ye, cap_saved = self.caption_fwd(y, row_idx, L, drop, y_null)
             if tkey is not None:
-                ctx["kvc"] = [None] * depth
-                self._text_cache = dict(key=tkey, ye=ye, kvc=ctx["kvc"], y=y)      # holds y so that its address cannot be reused by another tensor
-        ctx["ye"] = ye
+                ctx.kvc = [None] * depth
+                self._text_cache = dict(key=tkey, ye=ctx.ye, kvc=ctx.kvc, y=y)      # holds y so that its address cannot be reused by another tensor
         xt = ops.patch_embed_fwd(x, S.f("x_embedder.proj.weight"), S.f("x_embedder.proj.bias"), self.pos_table(h, w))
         x_prev, u_prev, gate_prev = xt, None, None
         blocks = []
         for l in range(depth):
             x_prev, u_prev, gate_prev, sv = self.block_fwd(l, x_prev, u_prev, gate_prev, ctx)
-            blocks.append(sv if save == "all" else (dict(x_in=sv["x_in"]) if save == "ckpt" else None))
+            blocks.append(sv if save == "all" else (BlockSaved(x_in=sv.x_in) if save == "ckpt" else None))
         r = ops.ln_mod_fwd(x_prev, fin_mod[:, 0], fin_mod[:, 1], 2 * D, u=u_prev, gate=gate_prev, gate_stride=6 * D, rows_per_batch=N, want_stats=True)
         lin = ops.gemm(r["xn"], S.w("final_layer.linear.weight"), NT, bias=S.f("final_layer.linear.bias"), out_dtype=F32)
         out = ops.unpatchify_fwd(lin, B, h, w, c["out_channels"])
         saved = None
         if save:
-            saved = dict(ctx=ctx, blocks=blocks, cap=cap_saved, x=x, x3=r["x"], meanf=r["mean"], rstdf=r["rstd"], xnf=r["xn"], fin_mod=fin_mod, mode=save)
+            saved = Saved(ctx=ctx, blocks=blocks, cap=cap_saved, x=x, x3=r["x"], meanf=r["mean"], rstdf=r["rstd"], xnf=r["xn"], fin_mod=fin_mod, mode=save)
         return out, saved
 
     def backward(self, dout, saved):
         """dout (B,2C,Hl,Wl) fp32 -> (dmod (L,B,6,D), dfin (B,2,D)); parameter gradients go to the flat buffer."""
         S, c = self.S, self.cfg
-        ctx = saved["ctx"]
-        B, N, D, depth = ctx["B"], ctx["N"], c["hidden_size"], c["depth"]
-        h, w = ctx["hw"]
+        ctx = saved.ctx
+        B, N, D, depth = ctx.B, ctx.N, c["hidden_size"], c["depth"]
+        h, w = ctx.hw
         dev = dout.device
-        ctx["dmod"] = torch.zeros_like(ctx["mod"])
-        dfin = torch.zeros_like(saved["fin_mod"])
-        ctx["dye"] = torch.zeros(ctx["ye"].shape, dtype=F32, device=dev)
+        ctx.dmod = torch.zeros_like(ctx.mod)
+        dfin = torch.zeros_like(saved.fin_mod)
+        ctx.dye = torch.zeros(ctx.ye.shape, dtype=F32, device=dev)
         dlin = ops.patchify_bwd(dout.contiguous(), h, w)
-        dxn = self._lin_bwd(dlin, saved["xnf"], "final_layer.linear")
+        dxn = self._lin_bwd(dlin, saved.xnf, "final_layer.linear")
         G = torch.empty((B * N, D), dtype=F32, device=dev)
-        ops.ln_mod_bwd(dxn, saved["x3"], saved["meanf"], saved["rstdf"], saved["fin_mod"][:, 1], 2 * D, None, G, dfin[:, 0], dfin[:, 1], 2 * D, N)
+        ops.ln_mod_bwd(dxn, saved.x3, saved.meanf, saved.rstdf, saved.fin_mod[:, 1], 2 * D, None, G, dfin[:, 0], dfin[:, 1], 2 * D, N)
         if self.grad_ready_hook:
             self.grad_ready_hook("final")
-        ctx["need_grad_aux"] = True                      # the recomputed forwards of a checkpointed step feed block_bwd
+        ctx.need_grad_aux = True                         # the recomputed forwards of a checkpointed step feed block_bwd
         for l in reversed(range(depth)):
-            sv = saved["blocks"][l]
-            if saved["mode"] == "ckpt":   # recompute this block's activations from its saved input (auto_grad_checkpoint semantics)
+            sv = saved.blocks[l]
+            if saved.mode == "ckpt":   # recompute this block's activations from its saved input (auto_grad_checkpoint semantics)
                 sv = self._recompute(l, sv, ctx)
             G = self.block_bwd(l, G, sv, ctx)
-            saved["blocks"][l] = None
-        ops.patch_embed_bwd(saved["x"], G, S.g("x_embedder.proj.weight"), S.g("x_embedder.proj.bias"))
-        self.caption_bwd(ctx["dye"], saved["cap"])
-        return ctx["dmod"], dfin
+            saved.blocks[l] = None
+        ops.patch_embed_bwd(saved.x, G, S.g("x_embedder.proj.weight"), S.g("x_embedder.proj.bias"))
+        self.caption_bwd(ctx.dye, saved.cap)
+        return ctx.dmod, dfin
 
     def _recompute(self, l, sv, ctx):
         """Re-run block l forward from its saved input x_in (x_in already includes the previous block's gated MLP branch)."""
-        return self.block_fwd(l, sv["x_in"], None, None, ctx)[3]
+        return self.block_fwd(l, sv.x_in, None, None, ctx)[3]

@@ -191,31 +191,19 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, block, x, y, t, lens, HW):
         eng = block._engine_for_standalone()
         B, N, D = x.shape
-        dev = x.device
-        import numpy as np
-        from ... import ops
-        starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
         mod = (block.scale_shift_table.detach()[None] + t.detach().reshape(B, 6, D)).contiguous()[None]
-        c = dict(B=B, N=N, hw=HW, mod=mod, kv_len=torch.tensor(lens, dtype=torch.int32, device=dev),
-                 kv_start=torch.from_numpy(starts).to(dev), max_len=int(max(lens)),
-                 ye=y.detach().reshape(-1, D).to(ops.BF16).contiguous())
-        x2, u3, gl, sv = eng.block_fwd(0, x.detach().reshape(B * N, D).to(F32).contiguous(), None, None, c)
-        r = ops.ln_mod_fwd(x2, u=u3, gate=gl, gate_stride=6 * D, want_xn=False, rows_per_batch=N)
-        ctx.block, ctx.c, ctx.sv, ctx.shape = block, c, sv, (B, N, D)
-        return r["x"].view(B, N, D)
+        out, ctx.saved = eng.block_standalone_fwd(x.detach().reshape(B * N, D).to(F32).contiguous(), y.detach(), mod, lens, HW)
+        ctx.block, ctx.shape = block, (B, N, D)
+        return out.view(B, N, D)
 
     @staticmethod
     def backward(ctx, dout):
-        block, c, sv = ctx.block, ctx.c, ctx.sv
-        B, N, D = ctx.shape
+        block, (B, N, D) = ctx.block, ctx.shape
         eng = block._engine_for_standalone()
         eng.S.attach_grads()
-        c["dmod"] = torch.zeros_like(c["mod"])
-        c["dye"] = torch.zeros(c["ye"].shape, dtype=F32, device=dout.device)
-        G = eng.block_bwd(0, dout.to(F32).reshape(B * N, D).contiguous().clone(), sv, c)
-        dmod = c["dmod"][0]                                   # (B,6,D): d(table + t)
+        G, dmod, dye = eng.block_standalone_bwd(dout.to(F32).reshape(B * N, D).contiguous().clone(), ctx.saved)      # dmod (B,6,D): d(table + t)
         block.scale_shift_table.grad.add_(dmod.sum(0))
-        return None, G.view(B, N, D), c["dye"].view(1, -1, D), dmod.reshape(B, 6 * D), None, None
+        return None, G.view(B, N, D), dye.view(1, -1, D), dmod.reshape(B, 6 * D), None, None
 
 
 # ----------------------------------------------------------------------------- modules

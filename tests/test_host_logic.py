@@ -284,7 +284,7 @@ def test_keys_resident_attention_refuses_a_sample_longer_than_max_kv_len():
     import inspect
     from pixart_sigma_amd import engine
     src = inspect.getsource(engine.Engine)
-    assert src.count("kv_len_host=ctx.get(\"lens_host\")") == 2          # both cross-attention call sites pass the host lengths
+    assert src.count("kv_len_host=ctx.lens_host") == 2          # both cross-attention call sites pass the host lengths (StepCtx.lens_host)
 
 
 def test_small_kernel_edge_references_on_cpu():
