@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define PXA_ABI_VERSION 10
+#define PXA_ABI_VERSION 11
 /* Kernels that fuse a bias-gradient column sum add into one of PXA_COLSUM_SLOTS partial rows ([slot][stride] fp32, caller-zeroed),
  * chosen per sample / row tile, so no address sees thousands of atomics; pxa_colsum_reduce folds the partials into the gradient. */
 #define PXA_COLSUM_SLOTS 16
@@ -311,6 +311,15 @@ int pxa_vae_im2col3x3(const pxa_grid* x, const float* mean, const float* rstd, c
 int pxa_vae_add(const pxa_grid* a, const pxa_grid* b, const pxa_grid* out, hipStream_t stream);
 /* P[r][:] = softmax(scale * S[r][:]) with fp32 scores in, bf16 probabilities out (mid-block attention: one 512-wide head). */
 int pxa_vae_softmax_rows(const float* s, long ld, void* p_bf16, long ldp, int rows, int cols, float scale, hipStream_t stream);
+/* (ABI 11) The whole mid-block attention in one streaming launch: O[b] = softmax(scale * Q[b] K[b]^T) V[b] for B images of HW tokens each, one head of
+ * width C (512, or 256) - diffusers AutoencoderKL mid_block.attentions[0], which the reference reaches through vae.decode / vae.encode (scripts/inference.py:136,
+ * train_scripts/train.py:149-153) and diffusers runs through SDPA.  It replaces, per image, the pxa_gemm (NT, fp32 HW x HW scores) -> pxa_vae_softmax_rows ->
+ * pxa_gemm (NN) chain: no score or probability matrix, no scratch, nothing allocated, capturable in a graph.  q, k, v: row (b * HW + token) at
+ * ptr + row * ld (elements of the operand type; e.g. the three column slices of the packed (B*HW, 3C) projection, ld = 3C); o likewise with ldo.
+ * Every ld >= C and a multiple of 8, every pointer 16-byte aligned; any HW >= 1.  Scores and softmax statistics fp32, P rounded to the operand type in
+ * front of P V, O accumulated in fp32 and rounded once.  Returns -1 on bad arguments, -3 when the kernel's LDS (128 KiB at C = 512) cannot be claimed. */
+int pxa_vae_attn(const void* q, const void* k, const void* v, long ldq, long ldk, long ldv, void* o, long ldo, int B, int HW, int C, float scale,
+                 hipStream_t stream);
 /* fp32 NCHW (B, C, H, W) image / latent -> bf16 grid scaled by mul, channels C..grid.C-1 zero; and back (first C channels). */
 int pxa_vae_nchw_to_grid(const float* img, int C, float mul, const pxa_grid* y, hipStream_t stream);
 int pxa_vae_grid_to_nchw(const pxa_grid* x, int C, float* img, hipStream_t stream);

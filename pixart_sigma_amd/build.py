@@ -23,7 +23,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # Per-source flags.  attn.hip: the SLP vectoriser packs adjacent scalar fp32 multiplies / adds of the softmax into v_pk_* instructions, which cost more
 # issue time beside MFMAs than the scalar forms they replace (MI355X_MICROARCH.md, price of fillers) and re-pair values against the bf16 packing:
 # without it forward -1.3 %, dK/dV -1.9 %, dQ (with delta folded into dP) -3.6 % (profiles/r02n_attn_fold_ab.txt).
-PER_FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize"]}
+# vae_attn.hip: its 128 output accumulators are scaled on the VALU when a row maximum moves.  Left to itself the compiler keeps them in AGPRs across the tile loop
+# and copies all of them to VGPRs and back around every key tile (256 v_accvgpr moves per tile beside 64 MFMAs, 976 in the code object); with the MFMAs
+# selected in their VGPR form the kernel is 256 VGPRs, no AGPR, no move, no scratch.
+PER_FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "vae_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _hipcc():

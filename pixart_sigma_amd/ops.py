@@ -477,6 +477,21 @@ def vae_softmax_rows(s, scale, out=None):
     return out
 
 
+def vae_attention(q, k, v, B, HW, scale, out=None):
+    """softmax(scale * q[b] k[b]^T) v[b] for B images of HW tokens in one streaming launch (pxa_vae_attn): (B*HW, C) of the operand type.  q, k, v: (B*HW, C)
+    with unit column stride and any row stride (e.g. the column slices of the packed qkv projection); C = 512 or 256; no score buffers, no scratch."""
+    rows, C = q.shape
+    for name, x in (("q", q), ("k", k), ("v", v)):
+        _chk(x, BF16, name)
+        assert tuple(x.shape) == (B * HW, C) and x.stride(1) == 1, f"vae_attention: {name} must be (B*HW, C) with unit column stride"
+    if out is None:
+        out = torch.empty(rows, C, dtype=BF16, device=q.device)
+    _chk(out, BF16, "out")
+    assert tuple(out.shape) == (rows, C) and out.stride(1) == 1
+    call("pxa_vae_attn", ptr(q), ptr(k), ptr(v), q.stride(0), k.stride(0), v.stride(0), ptr(out), out.stride(0), B, HW, C, scale)
+    return out
+
+
 def vae_nchw_to_grid(img, y, mul=1.0):
     _chk(img, F32, "image")
     assert img.is_contiguous() and img.shape[0] == y.B and img.shape[2] == y.H and img.shape[3] == y.W

@@ -7,7 +7,8 @@
 The parameters live in nn.Conv2d / nn.GroupNorm / nn.Linear containers under diffusers' state-dict names (so its checkpoints load
 unchanged); the containers' own forwards are never called.  Compute: bf16 NHWC pixel grids, every convolution a pxa_gemm (3x3
 stride 1: implicit GEMM over the zero-padded grid, see include/pixart_hip.h), GroupNorm/SiLU/upsampling/residual/softmax kernels
-from csrc/vae.hip.  Forward only: the reference keeps the VAE frozen under torch.no_grad().  There is no CPU / eager fallback -
+from csrc/vae.hip, the mid-block attention either as that score GEMM / softmax / P V chain or as one streaming launch (csrc/vae_attn.hip;
+set_attention / attention_plan below).  Forward only: the reference keeps the VAE frozen under torch.no_grad().  There is no CPU / eager fallback -
 without libpixart_hip.so and a GPU every call raises.
 """
 import json
@@ -29,6 +30,26 @@ def _img_rows(H, W):
     """Pixel slots per image of a zero-bordered (H+2) x (W+2) grid, rounded up to the GEMM's 256-row tile: every output tile of an
     implicit convolution then belongs to one image (the GroupNorm statistics of its epilogue need that) and M has no partial tile."""
     return ((H + 2) * (W + 2) + 255) // 256 * 256
+
+
+ATTENTION_MODES = ("auto", "scores", "streaming")
+STREAMING_WIDTHS = (512, 256)            # head widths pxa_vae_attn is built for
+AUTO_STREAMING_ABOVE = 65536             # H*W above which "auto" streams: one fp32 + 16-bit score pair alone would pass 100 GB
+
+
+def attention_plan(mode, HW, C):
+    """Which mid-block attention path runs: "scores" (per image: fp32 HW x HW score GEMM, pxa_vae_softmax_rows, P V GEMM; images alternate over two streams;
+    H*W a multiple of 8) or "streaming" (one pxa_vae_attn launch over all images: no score buffers, no side streams, any H*W).  "auto" is the scores path at
+    every H*W it can hold (<= 65536, the 2K config), and streaming above where the kernel has the width - it never fails where "scores" would have run."""
+    if mode not in ATTENTION_MODES:
+        raise ValueError(f"VAE attention mode must be one of {ATTENTION_MODES}, got {mode!r}")
+    if mode == "streaming":
+        if C not in STREAMING_WIDTHS:
+            raise ValueError(f"streaming VAE attention is built for widths {STREAMING_WIDTHS}, not {C}")
+        return "streaming"
+    if mode == "auto" and HW > AUTO_STREAMING_ABOVE and C in STREAMING_WIDTHS:
+        return "streaming"
+    return "scores"
 
 
 class DiagonalGaussianDistribution:
@@ -159,6 +180,18 @@ class AutoencoderKL(nn.Module):
         self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
         self.requires_grad_(False)
         self._packed, self._packed_key, self._pad_cache = {}, None, {}
+        self._attention_mode = None                                  # None: PXA_VAE_ATTN (read per call), else "auto"
+
+    def set_attention(self, mode):
+        """Mid-block attention path: "auto" (default), "scores" or "streaming" (attention_plan); overrides the PXA_VAE_ATTN environment variable."""
+        if mode not in ATTENTION_MODES:
+            raise ValueError(f"VAE attention mode must be one of {ATTENTION_MODES}, got {mode!r}")
+        self._attention_mode = mode
+        return self
+
+    def attention_mode(self):
+        """The mode in force: set_attention's, else PXA_VAE_ATTN, else "auto"."""
+        return self._attention_mode if self._attention_mode is not None else os.environ.get("PXA_VAE_ATTN", "auto")
 
     # ------------------------------------------------------------------ checkpoint plumbing (diffusers directory layout)
     @classmethod
@@ -355,9 +388,19 @@ class AutoencoderKL(nn.Module):
 
     def _attention(self, x, at):
         B, HW, C, dev = x.B, x.H * x.W, x.C, x.buf.device
-        assert HW % 8 == 0, "mid-block attention: H*W must be a multiple of 8"
+        plan = attention_plan(self.attention_mode(), HW, C)
+        assert plan == "streaming" or HW % 8 == 0, "mid-block attention: H*W must be a multiple of 8"
         t = ops.vae_gn_apply(x, Grid.compact(B, x.H, x.W, C, dev), self._norm(x, at.group_norm))
         qkv = self._conv1(t, None, key=("qkv", id(at))).buf      # (B*HW, 3C)
+        if plan == "streaming":                                  # all images in ONE launch on the caller's stream: no score buffers, no side streams
+            o = ops.vae_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, HW, C ** -0.5)
+        else:
+            o = self._attention_scores(qkv, B, HW, C, dev)
+        o = self._conv1(Grid(o, B, x.H, x.W, C), at.to_out[0])
+        return ops.vae_add(o, x, o)
+
+    def _attention_scores(self, qkv, B, HW, C, dev):
+        """softmax(q k^T / sqrt(C)) v of every image through an HW x HW score matrix: (B*HW, C)."""
         o = torch.empty(B * HW, C, dtype=BF16, device=dev)
         # scores of one image at a time (HW x HW fp32).  Round 6: the images alternate over PXA_VAE_ATTN_STREAMS (default 2) HIP streams - the P V product of one
         # image (an NN GEMM of 128 workgroups: half the CUs, 66 us) runs beside the next image's score GEMM and softmax instead of in front of them.  Every
@@ -383,8 +426,7 @@ class AutoencoderKL(nn.Module):
                 done = torch.cuda.Event()
                 done.record(st)
                 main.wait_event(done)
-        o = self._conv1(Grid(o, B, x.H, x.W, C), at.to_out[0])
-        return ops.vae_add(o, x, o)
+        return o
 
     def _side_streams(self, dev, n):
         key = (str(dev), n)

@@ -1,5 +1,5 @@
 """VAE decode / encode throughput on the HIP kernel set (config 5 of BASELINE.json is VAE-decode-bound: 512px, batch 64/GPU).
-Usage (GPU box): python tools/bench_vae.py [--px 512] [--batch 16] [--iters 3] [--encode] [--cpu-sample]
+Usage (GPU box): python tools/bench_vae.py [--px 512] [--batch 16] [--iters 3] [--encode] [--cpu-sample] [--attention auto|scores|streaming]
 Prints one JSON line: images/s, ms per batch, algorithmic TFLOP (2*m*n*k of every convolution / projection / attention product
 at the UNPADDED sizes) and the achieved TFLOP/s; --cpu-sample times oracle/vae_ref.py (fp32, torch CPU) on one 256px image."""
 import argparse
@@ -47,10 +47,13 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--encode", action="store_true")
     ap.add_argument("--cpu-sample", action="store_true")
+    ap.add_argument("--attention", choices=("auto", "scores", "streaming"), default=None, help="mid-block attention path (AutoencoderKL.set_attention); default: PXA_VAE_ATTN / auto")
     a = ap.parse_args()
     from pixart_sigma_amd.vae import AutoencoderKL
     torch.manual_seed(0)
     vae = AutoencoderKL().cuda()                               # random-init weights (torch's default init; GroupNorm 1 / 0)
+    if a.attention is not None:
+        vae.set_attention(a.attention)
     if a.encode or a.cpu_sample:                               # the encoder's FLOP count and the CPU sample come from the restated reference (tools only)
         from oracle.vae_ref import AutoencoderKLRef, randomize_
         ref = randomize_(AutoencoderKLRef(), seed=0)
@@ -77,7 +80,8 @@ def main():
     ms = e0.elapsed_time(e1) / a.iters
     out = {"op": "vae_encode" if a.encode else "vae_decode", "px": a.px, "batch": a.batch, "ms_per_batch": ms, "images_per_s": a.batch / ms * 1e3,
            "algorithmic_tflop_per_image": fl / 1e12, "achieved_tflops": fl * a.batch / ms / 1e9, "mfma_peak_frac": fl * a.batch / ms / 1e9 / 2500.0,
-           "dtype": "bf16 storage / fp32 accumulate", "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
+           "dtype": "bf16 storage / fp32 accumulate", "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
+           "attention": vae.attention_mode()}
     if a.cpu_sample:
         torch.set_num_threads(os.cpu_count())
         xs = torch.randn(1, 4, 32, 32, generator=g)
