@@ -337,6 +337,33 @@ int pxa_vae_conv3x3_small_out(const pxa_grid* x, const float* mean, const float*
 int pxa_linear_f32_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, hipStream_t stream);
 int pxa_linear_f32_bwd(const float* dy, const float* x, const float* w, float* dx_zeroed, float* dw, float* db, int M, int N, int K, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- T5 text encoder
+ * The kernels of the T5 v1.1 encoder that are not GEMMs.  Reference: diffusion/model/t5.py:87,106-111 - transformers.T5EncoderModel.from_pretrained(...,
+ * torch_dtype=bfloat16) and model(input_ids, attention_mask)['last_hidden_state'].  The q / k / v / o projections and the gated feed-forward
+ * (gelu_new(wi_0 x) * wi_1 x, then wo) are pxa_gemm calls: act 1, then act 4 with aux = the first product; o and wo add into the fp32 residual stream
+ * through out_f32 + accumulate, so the residual has no kernel of its own.
+ * pxa_t5_embed: x[r][:] = float(table[ids[r]][:]) for R rows of width D (a multiple of 8); table [vocab][D] in the operand type, x fp32 [R][D], ids device
+ *   int32 [R].  An id outside [0, vocab) is clamped into it (no out-of-range address is formed); the caller validates ids on the host. */
+int pxa_t5_embed(const int* ids, const void* table, float* x, int R, int D, int vocab, hipStream_t stream);
+/* T5LayerNorm over fp32 rows: y = x * rsqrt(mean(x^2) + eps) * w - no mean subtraction, no bias; statistics fp32.  x [R][D], w [D]; y_bf16 (operand type,
+ * feeds a GEMM) and / or y_f32 (the final norm: caption features are fp32 downstream), [R][D] each, either may be NULL.  D a multiple of 8, any R >= 1. */
+int pxa_t5_rmsnorm(const float* x, const float* w, void* y_bf16, float* y_f32, int R, int D, float eps, hipStream_t stream);
+/* O[b,h] = softmax(Q K^T + bias[h][j - i] + keymask_b) V for B samples of L tokens and H heads of width 64, NO softmax scale (T5Attention).
+ * q, k, v, o: row (b * L + token) at ptr + row * ld (elements of the operand type), head h in columns 64 h .. 64 h + 63 - e.g. the three column slices of
+ * the packed (B*L, 3*H*64) projection.  Every ld >= H*64 and a multiple of 8, every pointer 16-byte aligned.  bias: fp32 [H][2L - 1], entry (j - i) + L - 1
+ * for query i and key j (the encoder is bidirectional: the relative-position bucket depends on the offset alone).  kv_len: device int32 [B],
+ * 1 <= kv_len[b] <= L; keys at or beyond it are excluded and never read.  Every query row is computed, rows of padded positions included, as
+ * T5EncoderModel does.  Scores and statistics fp32, P rounded to the operand type in front of P V, O accumulated in fp32 and rounded once.
+ * 1 <= L <= 512, 1 <= H <= 64, head_dim == 64.  No scratch, nothing allocated, capturable in a graph. */
+typedef struct {
+  const void* q; const void* k; const void* v; void* o;
+  long ldq, ldk, ldv, ldo;
+  const float* bias;
+  const int* kv_len;
+  int B, H, L, head_dim;
+} pxa_t5_attn_args;
+int pxa_t5_attn(const pxa_t5_attn_args* args, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------- measurement
  * The part's matrix rate under its power limit, for the `roofline` object of bench.py (no reference counterpart: the reference reports no roofline).
  * One launch = `iters` x 32 v_mfma_f32_32x32x16 (shape 32) or 64 v_mfma_f32_16x16x32 (shape 16) per wave on register-resident operand data, one wave per

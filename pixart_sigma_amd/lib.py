@@ -69,6 +69,14 @@ class AttnArgs(C.Structure):
                 ("bwd_stats", c_void_p), ("q_prescaled", c_int)]
 
 
+class T5AttnArgs(C.Structure):
+    """pxa_t5_attn_args (include/pixart_hip.h, T5 text encoder)."""
+    _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("o", c_void_p),
+                ("ldq", c_long), ("ldk", c_long), ("ldv", c_long), ("ldo", c_long),
+                ("bias", c_void_p), ("kv_len", c_void_p),
+                ("B", c_int), ("H", c_int), ("L", c_int), ("head_dim", c_int)]
+
+
 # name -> argtypes (all return int); must list every symbol include/pixart_hip.h declares
 _P, _I, _L, _F = c_void_p, c_int, c_long, c_float
 _G = C.POINTER(GridArg)
@@ -113,6 +121,9 @@ SIGNATURES = {
     "pxa_vae_nchw_to_grid": [_P, _I, _F, _G, _P],
     "pxa_vae_grid_to_nchw": [_G, _I, _P, _P],
     "pxa_vae_conv3x3_small_out": [_G, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P],
+    "pxa_t5_embed": [_P, _P, _P, _I, _I, _I, _P],
+    "pxa_t5_rmsnorm": [_P, _P, _P, _P, _I, _I, _F, _P],
+    "pxa_t5_attn": [C.POINTER(T5AttnArgs), _P],
 }
 OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan",
                  "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe"]

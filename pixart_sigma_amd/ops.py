@@ -7,7 +7,7 @@ import math
 import torch
 
 from . import lib
-from .lib import AttnArgs, GemmArgs, GridArg, call, ptr
+from .lib import AttnArgs, GemmArgs, GridArg, T5AttnArgs, call, ptr
 
 # BF16 = the process's 16-bit operand dtype: torch.bfloat16, or torch.float16 under PXA_OPERAND_DTYPE=f16 (historical name)
 from .lib import OPERAND_DTYPE as BF16  # noqa: E402
@@ -489,6 +489,66 @@ def vae_attention(q, k, v, B, HW, scale, out=None):
     _chk(out, BF16, "out")
     assert tuple(out.shape) == (rows, C) and out.stride(1) == 1
     call("pxa_vae_attn", ptr(q), ptr(k), ptr(v), q.stride(0), k.stride(0), v.stride(0), ptr(out), out.stride(0), B, HW, C, scale)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ T5 text encoder
+T5_MAX_L, T5_MAX_H, T5_HEAD_DIM = 512, 64, 64
+
+
+def t5_embed(ids, table, out=None):
+    """out[r] = float(table[ids[r]]) (pxa_t5_embed).  ids: int32 (R,), table: (vocab, D) of the operand type; returns fp32 (R, D)."""
+    _chk(table, BF16, "table")
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and table.is_contiguous()
+    R, (vocab, D) = ids.numel(), table.shape
+    if out is None:
+        out = torch.empty(R, D, dtype=F32, device=table.device)
+    _chk(out, F32, "out")
+    assert tuple(out.shape) == (R, D) and out.is_contiguous()
+    call("pxa_t5_embed", ptr(ids), ptr(table), ptr(out), R, D, vocab)
+    return out
+
+
+def t5_rmsnorm(x, w, eps=1e-6, out=None, out_f32=None, want_bf16=True, want_f32=False):
+    """T5LayerNorm rows (pxa_t5_rmsnorm): x (R, D) fp32, w (D,) fp32.  Returns (operand-type output or None, fp32 output or None)."""
+    _chk(x, F32, "x")
+    _chk(w, F32, "w")
+    R, D = x.shape
+    assert x.is_contiguous() and w.numel() == D
+    if out is None and want_bf16:
+        out = torch.empty(R, D, dtype=BF16, device=x.device)
+    if out_f32 is None and want_f32:
+        out_f32 = torch.empty(R, D, dtype=F32, device=x.device)
+    if out is not None:
+        _chk(out, BF16, "out")
+        assert tuple(out.shape) == (R, D) and out.is_contiguous()
+    if out_f32 is not None:
+        _chk(out_f32, F32, "out_f32")
+        assert tuple(out_f32.shape) == (R, D) and out_f32.is_contiguous()
+    call("pxa_t5_rmsnorm", ptr(x), ptr(w), ptr(out), ptr(out_f32), R, D, eps)
+    return out, out_f32
+
+
+def t5_attention(q, k, v, bias, kv_len, B, H, L, out=None):
+    """softmax(q k^T + bias[h][j - i] + key mask) v per (sample, head), head_dim 64, no scale (pxa_t5_attn).  q, k, v: (B*L, H*64) of the operand type with unit
+    column stride and any row stride (the column slices of the packed projection); bias: fp32 (H, 2L - 1); kv_len: int32 (B,) on the device."""
+    W = H * T5_HEAD_DIM
+    for name, x in (("q", q), ("k", k), ("v", v)):
+        _chk(x, BF16, name)
+        assert tuple(x.shape) == (B * L, W), f"t5_attention: {name} must be (B*L, H*64)"
+    _chk(bias, F32, "bias")
+    assert tuple(bias.shape) == (H, 2 * L - 1) and bias.is_contiguous()
+    assert kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.numel() == B and kv_len.is_contiguous()
+    if out is None:
+        out = torch.empty(B * L, W, dtype=BF16, device=q.device)
+    _chk(out, BF16, "out")
+    assert tuple(out.shape) == (B * L, W)
+    a = T5AttnArgs()
+    a.q, a.k, a.v, a.o = ptr(q), ptr(k), ptr(v), ptr(out)
+    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.bias, a.kv_len = ptr(bias), ptr(kv_len)
+    a.B, a.H, a.L, a.head_dim = B, H, L, T5_HEAD_DIM
+    call("pxa_t5_attn", C.byref(a))
     return out
 
 

@@ -2,7 +2,8 @@
 """Text-to-image sampling entry point with the reference's CLI (reference scripts/inference.py:24-44), on the MI355X
 denoiser.  The frozen side nets are outside this repo's scope: captions are read as
 precomputed T5 features (tools/extract_features.py format: .npz with `caption_feature` (1,L,4096) and `attention_mask`
-(1,L)) from `--caption_feats`, or drawn at random with `--synthetic` (there is no T5 in this repo); latents are decoded by the HIP VAE
+(1,L)) from `--caption_feats`, made from the prompts by the in-repo T5 encoder with `--t5_path DIR` (tools/extract_t5_features.py in a child process of its
+own: T5 runs under the bf16 operand build and its 9.5 GB of weights are gone before the denoiser loads), or drawn at random with `--synthetic`; latents are decoded by the HIP VAE
 (pixart_sigma_amd.vae.AutoencoderKL, reference inference.py:136,191-196) when the diffusers-format `vae/` directory exists, else
 saved as latents (`--random_vae` decodes with a random-init VAE: plumbing / timing runs without weights).
 
@@ -50,31 +51,60 @@ def get_args():
     p.add_argument("--kv_compress_scale", default=2, type=int)
     p.add_argument("--kv_compress_layers", default="14-27")
     p.add_argument("--synthetic", action="store_true", help="random caption features (plumbing check without T5 weights)")
+    p.add_argument("--t5_path", default=None, type=str, help="transformers T5 directory (weights + tokenizer): encode the prompts with the in-repo T5 encoder first")
+    p.add_argument("--t5_timeout", default=1800, type=int, help="seconds the T5 child process may take")
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
     return p.parse_args()
 
 
-def load_captions(args, n, L, dev):
+def load_captions(args, n, L, dev, first=0):
+    """Features and masks of prompts first .. first + n - 1 (files <idx>.npz of --caption_feats) and the null caption's features."""
     if args.synthetic:
         g = torch.Generator().manual_seed(args.seed)
         return torch.randn(n, 1, L, 4096, generator=g).to(dev), torch.ones(n, L, dtype=torch.int64), torch.randn(1, 1, L, 4096, generator=g).to(dev)
     import numpy as np
     feats, masks = [], []
     for i in range(n):
-        z = np.load(os.path.join(args.caption_feats, f"{i}.npz"))
-        feats.append(torch.from_numpy(z["caption_feature"]).float().reshape(1, 1, -1, 4096)[:, :, :L])
+        z = np.load(os.path.join(args.caption_feats, f"{first + i}.npz"))
+        feats.append(torch.from_numpy(z["caption_feature"]).float().reshape(1, 1, -1, z["caption_feature"].shape[-1])[:, :, :L])
         masks.append(torch.from_numpy(z["attention_mask"]).reshape(1, -1)[:, :L])
     null = np.load(os.path.join(args.caption_feats, "null.npz"))
-    return torch.cat(feats).to(dev), torch.cat(masks), torch.from_numpy(null["caption_feature"]).float().reshape(1, 1, -1, 4096)[:, :, :L].to(dev)
+    return torch.cat(feats).to(dev), torch.cat(masks), torch.from_numpy(null["caption_feature"]).float().reshape(1, 1, -1, null["caption_feature"].shape[-1])[:, :, :L].to(dev)
+
+
+def t5_child_command(args, prompts_file, out_dir, L):
+    """The command line of the T5 child process of --t5_path (tools/extract_t5_features.py)."""
+    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "extract_t5_features.py")
+    return [sys.executable, tool, "--t5_path", args.t5_path, "--prompts", prompts_file, "--out", out_dir, "--max_length", str(L)]
+
+
+def encode_prompts(args, prompts, L):
+    """--t5_path: caption features of `prompts` into output/<save_name>/caption_feats by a fresh child process, BEFORE this process touches the GPU (one operand
+    build per process: the child pins bf16, this one defaults to fp16; and the T5 weights do not stay resident beside the denoiser).  Returns the directory."""
+    import subprocess
+    out_dir = os.path.join("output", args.save_name, "caption_feats")
+    os.makedirs(out_dir, exist_ok=True)
+    prompts_file = os.path.join(out_dir, "prompts.txt")
+    with open(prompts_file, "w") as f:
+        f.write("\n".join(prompts) + "\n")
+    env = dict(os.environ, PXA_OPERAND_DTYPE="bf16")
+    env.pop("PXA_LIB_PATH", None)
+    r = subprocess.run(t5_child_command(args, prompts_file, out_dir, L), env=env, timeout=args.t5_timeout)
+    if r.returncode != 0:
+        raise SystemExit(f"--t5_path: the T5 encoder process failed (exit {r.returncode})")
+    return out_dir
 
 
 @torch.no_grad()
 def main():
     args = get_args()
+    L = {"alpha": 120, "sigma": 300}[args.version]
+    prompts = [ln.strip() for ln in open(args.txt_file)] if os.path.exists(args.txt_file) else [f"prompt {i}" for i in range(args.bs)]
+    if args.t5_path and not args.synthetic:
+        args.caption_feats = encode_prompts(args, prompts, L)
     dev = torch.device("cuda")
     torch.manual_seed(args.seed)
     latent = args.image_size // 8
-    L = {"alpha": 120, "sigma": 300}[args.version]
     steps = args.step if args.step > 0 else {"iddpm": 100, "dpm-solver": 20, "sa-solver": 25}[args.sampling_algo]           # reference inference.py:159-160
     kvc = None
     if args.kv_compress:
@@ -93,12 +123,11 @@ def main():
         vae = AutoencoderKL.from_pretrained(vae_dir).to(dev).to(torch.float16)
     elif args.random_vae:
         vae = AutoencoderKL(scaling_factor=0.18215 if args.sdvae else 0.13025).to(dev).to(torch.float16)
-    prompts = [ln.strip() for ln in open(args.txt_file)] if os.path.exists(args.txt_file) else [f"prompt {i}" for i in range(args.bs)]
     os.makedirs(os.path.join("output", args.save_name), exist_ok=True)
     for start in range(0, len(prompts), args.bs):
         chunk = prompts[start:start + args.bs]                      # bs == 1 works (reference indexes prompts[0] before appending)
         n = len(chunk)
-        y, mask, null_y = load_captions(args, n, L, dev)
+        y, mask, null_y = load_captions(args, n, L, dev, first=start if args.t5_path else 0)      # --t5_path wrote one file per prompt line
         hw = torch.tensor([[args.image_size, args.image_size]] * n, dtype=torch.float, device=dev)
         ar = torch.ones(n, 1, device=dev)
         z = torch.randn(n, 4, latent, latent, device=dev)

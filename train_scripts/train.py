@@ -6,7 +6,8 @@
 Data: precomputed features in the reference's layout (tools/extract_features.py: `<name>.npy` = cat[mean,std] latent,
 `<name>.npz` = caption_feature + attention_mask) listed in `config.data_root`, or `--synthetic`.  With `load_vae_feat = False`
 the batches are images and the latents come from the HIP VAE on the fly, as in reference train.py:144-153 (`vae_pretrained` = a
-diffusers AutoencoderKL directory; synthetic images and a random-init VAE when it is absent).  T5 on the fly, mmcv
+diffusers AutoencoderKL directory; synthetic images and a random-init VAE when it is absent).  Caption features are made ahead of
+training (tools/extract_t5_features.py: the in-repo T5 encoder, pixart_sigma_amd.t5); T5 inside the training loop, mmcv
 configs with `_base_` inheritance, tensorboard/wandb trackers and validation image logging are outside this repo's scope
 (SURVEY.md section 2): the config is a plain Python file whose module-level names are the keys of section 5 of the survey.
 """
