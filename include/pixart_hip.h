@@ -181,6 +181,14 @@ int pxa_attn_fwd(const pxa_attn_args* args, hipStream_t stream);
 /* backward: delta pre-pass, then the dQ kernel (skipped when dq == NULL) and the dK/dV kernel (skipped when dk == dv == NULL) */
 int pxa_attn_bwd(const pxa_attn_args* args, hipStream_t stream);
 long pxa_attn_bwd_stats_bytes(int B, int H, int Nq);
+/* What pxa_attn_fwd (backward == 0) or pxa_attn_bwd (backward != 0) would launch for `args`, as one line of text in `out` - through the same checks, knobs
+ * and choice, launching nothing (pointers are only compared with NULL; no GPU is needed for shapes whose keys cannot stay resident in LDS: more than 320
+ * keys per sample or fewer than 512 queries - the others ask the device for the large-LDS opt-in, as the entry points do).
+ *   forward:   "fwd=<kvres|fwd4|fwd2|fwd1> fwd_kernel=<kernel> fwd_nx=<blocks per (batch, head)>"
+ *   backward:  "pre=<none|rows|strided> dq=<kvres|dq4|dq2|r2|skip> dkv=<dkv4|dkv2|dkv2_plain|dkv5|dkv3|r2|skip> pre_kernel=<kernel> dq_kernel=<kernel> dq_nx=<n>
+ *               dkv_kernel=<kernel> dkv_nx=<n>"   (one line; "-" and 0 for a stage that is skipped)
+ * A call the entry point refuses is refused here with the same return code and pxa_last_error(). */
+int pxa_attn_plan(const pxa_attn_args* args, int backward, char* out, int out_len);
 
 /* ---------------------------------------------------------------------------------------------- token boundary
  * PatchEmbed conv (k=2,s=2) + bias + pos_embed -> fp32 tokens (PixArtMS.py:38-44,184); its weight/bias gradient;

@@ -2606,19 +2606,49 @@ enum class AttnPre { none, rows, strided };                     // attn_delta_ro
 enum class AttnDq { kvres, dq4, dq2, r2 };                      // attn_bwd_dq_kvres_kernel, attn_bwd_dq4_kernel, attn_bwd_dq2_kernel; attn_ab.h: attn_bwd_dq_kernel
 enum class AttnDkv { dkv4, dkv2, dkv2_plain, dkv5, dkv3, r2 };  // attn_bwd_dkv4_kernel, attn_bwd_dkv2_kernel<1> / <0>; attn_ab.h: dkv5, dkv3, attn_bwd_dkv_kernel
 
-bool fwd_kvres_available() { return lds_optin(reinterpret_cast<const void*>(attn_fwd_kvres_kernel), KVRES_TILES * 2 * TILE_B) == hipSuccess; }
-
-int launch_fwd(AttnFwd k, AttnParams p, int max_k, hipStream_t stream) {
+// Blocks per (batch, head) of each kernel - p.nx, and qpb = the queries per workgroup of the keys-resident kernels - with the launchers' grid checks: the
+// launchers and pxa_attn_plan share them.
+int fwd_grid(AttnFwd k, AttnParams& p, int& qpb) {
   if (k == AttnFwd::kvres) {
-    const int tiles = (max_k + BKV - 1) / BKV, lds = tiles * 2 * TILE_B;
-    const int qpb = p.Nq >= 4096 ? 4096 : (p.Nq + 511) / 512 * 512;        // a whole head per workgroup up to 4,096 queries
+    qpb = p.Nq >= 4096 ? 4096 : (p.Nq + 511) / 512 * 512;        // a whole head per workgroup up to 4,096 queries
     p.nx = (p.Nq + qpb - 1) / qpb;
-    hipLaunchKernelGGL(attn_fwd_kvres_kernel, dim3(p.nx * p.H * p.B), dim3(512), lds, stream, p, qpb, tiles);
-    PXA_LAUNCH_CHECK();
     return 0;
   }
   p.nx = k == AttnFwd::fwd1 ? (p.Nq + 127) / 128 : (p.Nq + 255) / 256;
   PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_fwd: grid too large");
+  return 0;
+}
+
+int dq_grid(AttnDq k, AttnParams& p, int& qpb) {
+  if (k == AttnDq::kvres) {
+    qpb = p.Nq >= 4096 ? 4096 : (p.Nq + 255) / 256 * 256;
+    p.nx = (p.Nq + qpb - 1) / qpb;
+    return 0;
+  }
+  p.nx = (p.Nq + 127) / 128;
+  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
+  if (k == AttnDq::dq4) p.nx = (p.Nq + 255) / 256;
+  return 0;
+}
+
+int dkv_grid(AttnDkv k, AttnParams& p, int max_k) {
+  const bool keys128 = k == AttnDkv::dkv2 || k == AttnDkv::dkv2_plain || k == AttnDkv::r2;     // the others take 256 keys per workgroup
+  p.nx = keys128 ? (max_k + 127) / 128 : (max_k + 255) / 256;
+  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
+  return 0;
+}
+
+bool fwd_kvres_available() { return lds_optin(reinterpret_cast<const void*>(attn_fwd_kvres_kernel), KVRES_TILES * 2 * TILE_B) == hipSuccess; }
+
+int launch_fwd(AttnFwd k, AttnParams p, int max_k, hipStream_t stream) {
+  int qpb = 0;
+  if (int rc = fwd_grid(k, p, qpb)) return rc;
+  if (k == AttnFwd::kvres) {
+    const int tiles = (max_k + BKV - 1) / BKV, lds = tiles * 2 * TILE_B;
+    hipLaunchKernelGGL(attn_fwd_kvres_kernel, dim3(p.nx * p.H * p.B), dim3(512), lds, stream, p, qpb, tiles);
+    PXA_LAUNCH_CHECK();
+    return 0;
+  }
   const dim3 grid(p.nx * p.H * p.B), block(256);
   if (k == AttnFwd::fwd4) hipLaunchKernelGGL(attn_fwd4_kernel, grid, block, 0, stream, p);
   else if (k == AttnFwd::fwd2) hipLaunchKernelGGL(attn_fwd2_kernel, grid, block, 0, stream, p);
@@ -2648,18 +2678,15 @@ int launch_prepass(AttnPre k, const AttnParams& p, float* delta, bf16_t* stats, 
 }
 
 int launch_dq(AttnDq k, bool prescaled, AttnParams p, int max_k, float* delta, bf16_t* stats, float inv_c, hipStream_t stream) {
+  int qpb = 0;
+  if (int rc = dq_grid(k, p, qpb)) return rc;
   if (k == AttnDq::kvres) {
     const int tiles = (max_k + BKV - 1) / BKV, lds = tiles * 2 * TILE_B;
-    const int qpb = p.Nq >= 4096 ? 4096 : (p.Nq + 255) / 256 * 256;
-    p.nx = (p.Nq + qpb - 1) / qpb;
     hipLaunchKernelGGL(attn_bwd_dq_kvres_kernel, dim3(p.nx * p.H * p.B), dim3(512), lds, stream, p, qpb, tiles, delta, stats, inv_c);
     PXA_LAUNCH_CHECK();
     return 0;
   }
-  p.nx = (p.Nq + 127) / 128;
-  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
   if (k == AttnDq::dq4) {
-    p.nx = (p.Nq + 255) / 256;
     if (prescaled) hipLaunchKernelGGL(attn_bwd_dq4_kernel<true>, dim3(p.nx * p.H * p.B), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(attn_bwd_dq4_kernel<false>, dim3(p.nx * p.H * p.B), dim3(256), 0, stream, p);
   } else hipLaunchKernelGGL(attn_bwd_dq2_kernel, dim3(p.nx * p.H * p.B), dim3(256), 0, stream, p);
@@ -2668,8 +2695,7 @@ int launch_dq(AttnDq k, bool prescaled, AttnParams p, int max_k, float* delta, b
 }
 
 int launch_dkv(AttnDkv k, bool prescaled, AttnParams p, int max_k, hipStream_t stream) {
-  p.nx = k == AttnDkv::dkv4 ? (max_k + 255) / 256 : (max_k + 127) / 128;
-  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
+  if (int rc = dkv_grid(k, p, max_k)) return rc;
   if (p.nx > 0) {
     const dim3 grid(p.nx * p.H * p.B), block(256);
     if (k == AttnDkv::dkv4 && prescaled) hipLaunchKernelGGL(attn_bwd_dkv4_kernel<true>, grid, block, 0, stream, p);
@@ -2797,46 +2823,109 @@ AttnDkv choose_dkv(const AttnParams& p, const Knobs& k) {
 }
 }  // namespace
 
-// ------------------------------------------------------------------------------------------------ entry points
-extern "C" int pxa_attn_fwd(const pxa_attn_args* a, hipStream_t stream) {
-  AttnParams p;
+// ------------------------------------------------------------------------------------------------ plan + entry points
+namespace {
+// What one call runs: pxa_attn_fwd / pxa_attn_bwd launch it, pxa_attn_plan prints it.
+struct AttnPlan {
+  int max_k;
+  AttnFwd fwd;
+  AttnPre pre;
+  AttnDq dq;
+  AttnDkv dkv;
+  bf16_t* stats;      // the statistics rows: written by the pre-pass for every dK/dV kernel but the round-2 one
+};
+
+int plan_fwd(const pxa_attn_args* a, AttnParams& p, AttnPlan& g) {
   if (int rc = fill(p, a)) return rc;
   PXA_CHECK(p.Q && p.K && p.V && p.O, "pxa_attn_fwd: null tensor");
   const Knobs k = read_knobs(false);
-  const int max_k = a->max_kv_len > 0 ? a->max_kv_len : p.Nk;
-  return launch_fwd(choose_fwd(p, max_k, k), p, max_k, stream);
+  g.max_k = a->max_kv_len > 0 ? a->max_kv_len : p.Nk;
+  g.fwd = choose_fwd(p, g.max_k, k);
+  return 0;
 }
 
-extern "C" long pxa_attn_bwd_stats_bytes(int B, int H, int Nq) { return 2L * B * H * ((Nq + BKV - 1) / BKV * BKV) * 16; }
-
-extern "C" int pxa_attn_bwd(const pxa_attn_args* a, hipStream_t stream) {
-  AttnParams p;
+int plan_bwd(const pxa_attn_args* a, AttnParams& p, AttnPlan& g) {
   if (int rc = fill(p, a)) return rc;
   PXA_CHECK(p.Q && p.K && p.V && p.O && p.dO && p.LSE && a->delta, "pxa_attn_bwd: null tensor");
   PXA_CHECK((p.dQ || p.dK) && (!p.dK == !p.dV), "pxa_attn_bwd: need dq and/or both of dk, dv (a NULL gradient skips the kernel that produces it)");
   for (long s : {p.dq_ts, p.dk_ts, p.dv_ts, (long)p.dq_hs, (long)p.dk_hs, (long)p.dv_hs, p.dq_bs, p.dk_bs, p.dv_bs})
     PXA_CHECK(s % 4 == 0, "pxa_attn_bwd: gradient strides must be multiples of 4 elements");
   const Knobs k = read_knobs(true);
-  const int max_k = a->max_kv_len > 0 ? a->max_kv_len : p.Nk;
-  const bool pre = a->q_prescaled != 0;
+  g.max_k = a->max_kv_len > 0 ? a->max_kv_len : p.Nk;
+  g.dkv = choose_dkv(p, k);
+  const bool dq_kvres = choose_dq_kvres(p, g.max_k, k);
+  g.stats = g.dkv != AttnDkv::r2 ? (bf16_t*)a->bwd_stats : nullptr;
+  g.pre = choose_prepass(p, k, dq_kvres);
+  g.dq = dq_kvres ? AttnDq::kvres : choose_dq(p, k);      // (meaningful where p.dQ)
+  return 0;
+}
+}  // namespace
 
-  const AttnDkv dkv = choose_dkv(p, k);
-  const bool dq_kvres = choose_dq_kvres(p, max_k, k);
-  bf16_t* stats = dkv != AttnDkv::r2 ? (bf16_t*)a->bwd_stats : nullptr;      // the statistics rows: written by the pre-pass for every dK/dV kernel but the round-2 one
+extern "C" int pxa_attn_fwd(const pxa_attn_args* a, hipStream_t stream) {
+  AttnParams p; AttnPlan g;
+  if (int rc = plan_fwd(a, p, g)) return rc;
+  return launch_fwd(g.fwd, p, g.max_k, stream);
+}
+
+extern "C" long pxa_attn_bwd_stats_bytes(int B, int H, int Nq) { return 2L * B * H * ((Nq + BKV - 1) / BKV * BKV) * 16; }
+
+extern "C" int pxa_attn_bwd(const pxa_attn_args* a, hipStream_t stream) {
+  AttnParams p; AttnPlan g;
+  if (int rc = plan_bwd(a, p, g)) return rc;
+  const bool pre = a->q_prescaled != 0;
   const float inv_c = 1.0f / p.scale_log2;
 
-  if (int rc = launch_prepass(choose_prepass(p, k, dq_kvres), p, a->delta, stats, inv_c, stream)) return rc;
+  if (int rc = launch_prepass(g.pre, p, a->delta, g.stats, inv_c, stream)) return rc;
   if (p.dQ) {
-    const AttnDq dq = dq_kvres ? AttnDq::kvres : choose_dq(p, k);
-    const int rc = dq == AttnDq::r2 ? launch_dq_ab(p, stream) : launch_dq(dq, pre, p, max_k, a->delta, stats, inv_c, stream);
+    const int rc = g.dq == AttnDq::r2 ? launch_dq_ab(p, stream) : launch_dq(g.dq, pre, p, g.max_k, a->delta, g.stats, inv_c, stream);
     if (rc) return rc;
   }
   if (p.dK) {
-    switch (dkv) {
-      case AttnDkv::dkv4: case AttnDkv::dkv2: case AttnDkv::dkv2_plain: return launch_dkv(dkv, pre, p, max_k, stream);
-      case AttnDkv::dkv5: case AttnDkv::dkv3: case AttnDkv::r2: return launch_dkv_ab(dkv, pre, p, max_k, stream);
+    switch (g.dkv) {
+      case AttnDkv::dkv4: case AttnDkv::dkv2: case AttnDkv::dkv2_plain: return launch_dkv(g.dkv, pre, p, g.max_k, stream);
+      case AttnDkv::dkv5: case AttnDkv::dkv3: case AttnDkv::r2: return launch_dkv_ab(g.dkv, pre, p, g.max_k, stream);
     }
   }
+  return 0;
+}
+
+extern "C" int pxa_attn_plan(const pxa_attn_args* a, int backward, char* out, int out_len) {
+  AttnParams p; AttnPlan g;
+  int n, qpb = 0;
+  if (!backward) {
+    if (int rc = plan_fwd(a, p, g)) return rc;
+    if (int rc = fwd_grid(g.fwd, p, qpb)) return rc;
+    PXA_CHECK(out && out_len > 0, "pxa_attn_plan: no text buffer");
+    static const char* const name[] = {"kvres", "fwd4", "fwd2", "fwd1"};
+    static const char* const kernel[] = {"attn_fwd_kvres_kernel", "attn_fwd4_kernel", "attn_fwd2_kernel", "attn_fwd_kernel"};
+    n = snprintf(out, out_len, "fwd=%s fwd_kernel=%s fwd_nx=%d", name[(int)g.fwd], kernel[(int)g.fwd], p.nx);
+  } else {
+    if (int rc = plan_bwd(a, p, g)) return rc;
+    const bool pre = a->q_prescaled != 0;
+    static const char* const pre_name[] = {"none", "rows", "strided"};
+    static const char* const pre_kernel[] = {"-", "attn_delta_rows_kernel", "attn_delta_kernel"};
+    static const char* const dq_name[] = {"kvres", "dq4", "dq2", "r2"};
+    static const char* const dq_kernel[] = {"attn_bwd_dq_kvres_kernel", "attn_bwd_dq4_kernel", "attn_bwd_dq2_kernel", "attn_bwd_dq_kernel"};
+    static const char* const dkv_name[] = {"dkv4", "dkv2", "dkv2_plain", "dkv5", "dkv3", "r2"};
+    static const char* const dkv_kernel[] = {"attn_bwd_dkv4_kernel", "attn_bwd_dkv2_kernel<1>", "attn_bwd_dkv2_kernel<0>", "attn_bwd_dkv5_kernel", "attn_bwd_dkv3_kernel<2>",
+                                             "attn_bwd_dkv_kernel"};
+    int dq_nx = 0, dkv_nx = 0;
+    if (p.dQ) {
+      if (int rc = dq_grid(g.dq, p, qpb)) return rc;
+      dq_nx = p.nx;
+    }
+    if (p.dK) {
+      if (int rc = dkv_grid(g.dkv, p, g.max_k)) return rc;
+      dkv_nx = p.nx;
+    }
+    PXA_CHECK(out && out_len > 0, "pxa_attn_plan: no text buffer");
+    const bool dq_pre = p.dQ && g.dq == AttnDq::dq4, dkv_pre = p.dK && (g.dkv == AttnDkv::dkv4 || g.dkv == AttnDkv::dkv5);   // the instances templated on q_prescaled
+    n = snprintf(out, out_len, "pre=%s dq=%s dkv=%s pre_kernel=%s dq_kernel=%s%s dq_nx=%d dkv_kernel=%s%s dkv_nx=%d", pre_name[(int)g.pre],
+                 p.dQ ? dq_name[(int)g.dq] : "skip", p.dK ? dkv_name[(int)g.dkv] : "skip", pre_kernel[(int)g.pre],
+                 p.dQ ? dq_kernel[(int)g.dq] : "-", dq_pre ? (pre ? "<true>" : "<false>") : "", dq_nx,
+                 p.dK ? dkv_kernel[(int)g.dkv] : "-", dkv_pre ? (pre ? "<true>" : "<false>") : "", dkv_nx);
+  }
+  PXA_CHECK(n < out_len, "pxa_attn_plan: text buffer of %d bytes is too small", out_len);
   return 0;
 }
 

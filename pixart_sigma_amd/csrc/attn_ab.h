@@ -778,16 +778,15 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(AttnParams p) {
 }
 
 int launch_dq_ab(AttnParams p, hipStream_t stream) {
-  p.nx = (p.Nq + 127) / 128;
-  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
+  int qpb = 0;
+  if (int rc = dq_grid(AttnDq::r2, p, qpb)) return rc;
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(p.nx * p.H * p.B), dim3(256), 0, stream, p);
   PXA_LAUNCH_CHECK();
   return 0;
 }
 
 int launch_dkv_ab(AttnDkv k, bool prescaled, AttnParams p, int max_k, hipStream_t stream) {
-  p.nx = k == AttnDkv::r2 ? (max_k + 127) / 128 : (max_k + 255) / 256;
-  PXA_CHECK((long)p.nx * p.H * p.B < (1L << 31), "pxa_attn_bwd: grid too large");
+  if (int rc = dkv_grid(k, p, max_k)) return rc;
   if (p.nx > 0) {
     const dim3 grid(p.nx * p.H * p.B);
     if (k == AttnDkv::dkv5 && prescaled) hipLaunchKernelGGL(attn_bwd_dkv5_kernel<true>, grid, dim3(256), 0, stream, p);

@@ -125,7 +125,7 @@ SIGNATURES = {
     "pxa_t5_rmsnorm": [_P, _P, _P, _P, _I, _I, _F, _P],
     "pxa_t5_attn": [C.POINTER(T5AttnArgs), _P],
 }
-OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan",
+OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan", "pxa_attn_plan",
                  "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe"]
 
 _lib = None
@@ -154,6 +154,7 @@ def load():
     lib.pxa_attn_bwd_stats_bytes.argtypes, lib.pxa_attn_bwd_stats_bytes.restype = [c_int, c_int, c_int], c_long
     lib.pxa_gemm_set_dynamic_items.argtypes, lib.pxa_gemm_set_dynamic_items.restype = [c_int], c_int
     lib.pxa_gemm_plan.argtypes, lib.pxa_gemm_plan.restype = [C.POINTER(GemmArgs), C.c_char_p, c_int], c_int
+    lib.pxa_attn_plan.argtypes, lib.pxa_attn_plan.restype = [C.POINTER(AttnArgs), c_int, C.c_char_p, c_int], c_int
     lib.pxa_mfma_rate_probe_bytes.argtypes, lib.pxa_mfma_rate_probe_bytes.restype = [], c_long
     lib.pxa_mfma_rate_probe.argtypes, lib.pxa_mfma_rate_probe.restype = [c_void_p, c_int, c_int, c_void_p, C.POINTER(C.c_double), c_void_p], c_int
     if lib.pxa_abi_version() != ABI_VERSION:

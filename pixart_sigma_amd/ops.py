@@ -209,7 +209,9 @@ def colsum(dy, out):
 Q_PRESCALE = 72 ** -0.5 * 1.4426950408889634      # scale * log2 e of the denoiser's heads: what a prescaled q carries (pxa_attn_args.q_prescaled)
 
 
-def _attn_args(q, k, v, o, B, H, Nq, Nk, strides, kv_start=None, kv_len=None, max_kv_len=0, scale=None, head_dim=72, q_prescaled=False):
+def _attn_args(q, k, v, o, B, H, Nq, Nk, strides, kv_start=None, kv_len=None, max_kv_len=0, scale=None, head_dim=72, q_prescaled=False, cuda=True):
+    def ptr(t):     # cuda=False: attention_plan, where only the presence of a pointer matters
+        return lib.ptr(t, cuda)
     a = AttnArgs()
     a.q, a.k, a.v, a.o = ptr(q), ptr(k), ptr(v), ptr(o)
     (a.q_bs, a.q_ts, a.q_hs), (a.k_bs, a.k_ts, a.k_hs), (a.v_bs, a.v_ts, a.v_hs), (a.o_bs, a.o_ts, a.o_hs) = strides
@@ -267,6 +269,32 @@ def attention_bwd(q, k, v, o, d_o, lse, delta, dq, dk, dv, B, H, Nq, Nk, strides
     (a.dq_bs, a.dq_ts, a.dq_hs), (a.dk_bs, a.dk_ts, a.dk_hs), (a.dv_bs, a.dv_ts, a.dv_hs) = dstrides
     call("pxa_attn_bwd", a)            # dq=None skips the dQ kernel, dk=dv=None the dK/dV kernel
     del stats
+
+
+def attention_plan(q, k, v, o, *rest, colsums=(None, None, None), **kw):
+    """What attention_fwd (called with its arguments: q, k, v, o, lse, B, H, Nq, Nk, strides, ...) or attention_bwd (with its own: q, k, v, o, d_o, lse,
+    delta, dq, dk, dv, B, H, Nq, Nk, strides, dstrides, ...) would launch, as pxa_attn_plan's one line of text; raises what they would raise for a call
+    the library refuses.  Launches nothing and allocates nothing: the tensors may live on any device, only their presence, the shapes and the strides
+    matter (the statistics workspace attention_bwd would pass is stood in for by an address that is never used)."""
+    _check_max_kv_len(kw)
+    backward = len(rest) == 12
+    assert len(rest) in (6, 12), "attention_plan takes the positional arguments of attention_fwd or of attention_bwd"
+    p = lambda t: lib.ptr(t, cuda=False)   # noqa: E731
+    if backward:
+        d_o, lse, delta, dq, dk, dv, B, H, Nq, Nk, strides, dstrides = rest
+        a = _attn_args(q, k, v, o, B, H, Nq, Nk, strides, cuda=False, **kw)
+        a.bwd_stats = C.c_void_p(C.addressof(_Unallocated._somewhere)) if dk is not None else None
+        a.dq_colsum, a.dk_colsum, a.dv_colsum = (p(t) for t in colsums)
+        a.colsum_stride = next((t.stride(0) for t in colsums if t is not None), 0)
+        a.lse, a.delta, a.d_o, a.dq, a.dk, a.dv = p(lse), p(delta), p(d_o), p(dq), p(dk), p(dv)
+        (a.dq_bs, a.dq_ts, a.dq_hs), (a.dk_bs, a.dk_ts, a.dk_hs), (a.dv_bs, a.dv_ts, a.dv_hs) = dstrides
+    else:
+        lse, B, H, Nq, Nk, strides = rest
+        a = _attn_args(q, k, v, o, B, H, Nq, Nk, strides, cuda=False, **kw)
+        a.lse = p(lse)
+    buf = C.create_string_buffer(256)
+    lib.check(lib.load().pxa_attn_plan(C.byref(a), int(backward), buf, len(buf)), "pxa_attn_plan")
+    return buf.value.decode()
 
 
 def patch_embed_fwd(x, w, bias, pos, out=None):
