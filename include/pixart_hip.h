@@ -317,7 +317,8 @@ int pxa_vae_im2col3x3(const pxa_grid* x, const float* mean, const float* rstd, c
                       int silu, int stride, int pad, int Ho, int Wo, void* col_bf16, hipStream_t stream);
 /* out = a + b over the interior pixels (residual connections; the three grids may have different pitches). */
 int pxa_vae_add(const pxa_grid* a, const pxa_grid* b, const pxa_grid* out, hipStream_t stream);
-/* P[r][:] = softmax(scale * S[r][:]) with fp32 scores in, bf16 probabilities out (mid-block attention: one 512-wide head). */
+/* P[r][:] = softmax(scale * S[r][:]) with fp32 scores in, bf16 probabilities out (mid-block attention: one 512-wide head).
+ * cols, ld and ldp multiples of 4; s 16-byte aligned, p 8-byte aligned (rows are read as float4, written four elements at a time): else -1. */
 int pxa_vae_softmax_rows(const float* s, long ld, void* p_bf16, long ldp, int rows, int cols, float scale, hipStream_t stream);
 /* (ABI 11) The whole mid-block attention in one streaming launch: O[b] = softmax(scale * Q[b] K[b]^T) V[b] for B images of HW tokens each, one head of
  * width C (512, or 256) - diffusers AutoencoderKL mid_block.attentions[0], which the reference reaches through vae.decode / vae.encode (scripts/inference.py:136,

@@ -263,7 +263,12 @@ __global__ __launch_bounds__(256) void nchw_to_grid_kernel(const float* __restri
   for (int c0 = 0; c0 < y.C; c0 += 8) {
     float f[8];
 #pragma unroll
-    for (int e = 0; e < 8; e++) f[e] = (c0 + e < C) ? img[((long)b * C + c0 + e) * HW + p] * mul : 0.f;
+    for (int e = 0; e < 8; e++) {
+      f[e] = (c0 + e < C) ? img[((long)b * C + c0 + e) * HW + p] * mul : 0.f;
+      // the product is an fp32 value before the store rounds it, in both operand builds: left alone, the fp16 build fuses the multiply and the conversion
+      // into v_fma_mixlo_f16, which rounds the exact product once and differs from fp32-multiply-then-round on ties (tests/test_vae_kernel_forms_gpu.py)
+      asm volatile("" : "+v"(f[e]));
+    }
     *reinterpret_cast<uint4*>(dst + c0) = pack8(f);
   }
 }
@@ -370,6 +375,7 @@ extern "C" int pxa_vae_add(const pxa_grid* a, const pxa_grid* b, const pxa_grid*
 extern "C" int pxa_vae_softmax_rows(const float* s, long ld, void* p_bf16, long ldp, int rows, int cols, float scale, hipStream_t stream) {
   PXA_CHECK(s && p_bf16 && rows > 0 && cols > 0, "pxa_vae_softmax_rows: bad arguments");
   PXA_CHECK(cols % 4 == 0 && ld % 4 == 0 && ldp % 4 == 0, "pxa_vae_softmax_rows: cols / ld / ldp must be multiples of 4");
+  PXA_CHECK((uintptr_t)s % 16 == 0 && (uintptr_t)p_bf16 % 8 == 0, "pxa_vae_softmax_rows: s must be 16-byte and p 8-byte aligned (float4 loads, 4-element stores)");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, stream, s, ld, (bf16_t*)p_bf16, ldp, cols, scale);
   PXA_LAUNCH_CHECK();
   return 0;
