@@ -373,6 +373,29 @@ typedef struct {
 } pxa_t5_attn_args;
 int pxa_t5_attn(const pxa_t5_attn_args* args, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- LoRA adapters
+ * y = x (W + s B A)^T + b with A [r][K], B [N][r] stored transposed as Bt [r][N]: what peft's LoraLayer computes for the reference's fine-tuning scripts
+ * (train_scripts/train_pixart_lora_hf.py:505-524).  The adapter is folded into the 16-bit operand copy of W, so every forward / dX GEMM runs unchanged;
+ * the adapter gradients come from two rank-r products and never form dW.
+ *
+ * pxa_lora_merge: rows [lo, hi) of the [.][K] fp32 matrix `master` (row pitch ld):  v[n][k] = master[n][k] + s * sum_j Bt[j][n - lo] * A[j][k], evaluated in
+ * fp64 (j ascending, fused multiply-adds: where the adapter cancels the weight an fp32 sum is many 16-bit steps off) in an order that depends on nothing but the
+ * element, so two calls give the same bits; v is that value in fp32.  dst16 (row pitch ld_dst, row 0 = row 0 of master) receives v rounded to the operand type.  Optional: dst2_16 (row pitch ld_dst2) receives v * mul (an fp32 product) for rows in [mul_lo, mul_hi) and v for
+ * the others, rounded once (the q-prescaled copy of attn.qkv); dst_f32 (row pitch ld, may be `master` itself) receives v in fp32 (merge_and_unload).
+ * A [r][K] and Bt [r][ldbt] fp32, ldbt >= hi - lo.  K a multiple of 4, 1 <= r <= 64, pointers 16-byte aligned, pitches multiples of 4.
+ *
+ * pxa_lora_bwd:  t = x A16^T, u = dy Bt16^T (fp32 accumulators, each rounded ONCE to the operand type);  dA += s u^T x;  dBt += s t^T dy  (fp32).
+ * x [M][K] (row pitch ldx), dy [M][N] (row pitch lddy: may be a column block of a wider matrix), A16 [r][K], Bt16 [r][N] of the operand type; dA [r][K],
+ * dBt [r][N] fp32.  Any M >= 1, 1 <= r <= 64 (zero-padded to the MFMA tile inside), K and N multiples of 64; x / dy / A16 / Bt16 16-byte aligned, ldx and lddy
+ * multiples of 8.  Nothing past M, r, K or N is read.  ws: pxa_lora_bwd_ws_bytes(M, K, N, r) bytes, 256-byte aligned, owned by the caller: t and u
+ * (transposed) and the fp32 partials of every 1024-row split, each written by exactly one workgroup and summed in split order - no atomics, so the result
+ * is the same from call to call.  Launches one projection / gradient kernel pair (PXA_LORA_CHUNK_MB, an A/B knob: one pair per chunk of that many MB of x + dy rows), then one reduce. */
+int pxa_lora_merge(const float* master, long ld, int lo, int hi, int K, const float* A, const float* Bt, long ldbt, int r, float s, void* dst16, long ld_dst,
+                   void* dst2_16, long ld_dst2, int mul_lo, int mul_hi, float mul, float* dst_f32, hipStream_t stream);
+long pxa_lora_bwd_ws_bytes(long M, int K, int N, int r);
+int pxa_lora_bwd(const void* x, long ldx, const void* dy, long lddy, const void* A16, const void* Bt16, long M, int K, int N, int r, float s, float* dA,
+                 float* dBt, void* ws, long ws_bytes, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------- measurement
  * The part's matrix rate under its power limit, for the `roofline` object of bench.py (no reference counterpart: the reference reports no roofline).
  * One launch = `iters` x 32 v_mfma_f32_32x32x16 (shape 32) or 64 v_mfma_f32_16x16x32 (shape 16) per wave on register-resident operand data, one wave per

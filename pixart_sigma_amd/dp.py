@@ -250,7 +250,10 @@ class FusedAdamW:
 
     def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-10, weight_decay=3e-2, max_grad_norm=0.01, reducer=None, scaler=None):
         assert model._store is not None, "call model.prepare(device) (or run one forward) before building the optimizer"
-        self.model, self.store = model, model._store
+        # A model with trainable LoRA adapters: the optimizer works on the adapters' own flat store (same kernels, moments for the adapters alone); the engine's
+        # grad_ready_hook fires the same `blocks.{i}` labels, which are that store's groups.  More than one rank: replica equality is checked on the adapters
+        # below (fresh adapters are drawn per process: seed them alike or load the same file) - that path has not been run on more than one GPU.
+        self.model, self.store = model, self._live_store(model)
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.scaler = scaler
         dev = self.store.device
@@ -272,8 +275,16 @@ class FusedAdamW:
     def last_norm(self):
         return self.coef[1]
 
+    @staticmethod
+    def _live_store(model):
+        lo = getattr(model, "_lora", None)
+        if lo is not None and lo.trainable:
+            assert lo.store is not None, "call model.prepare(device) (or run one forward) after add_lora, before building the optimizer"
+            return lo.store
+        return model._store
+
     def _check_store(self):
-        if self.model._store is not self.store:
+        if self._live_store(self.model) is not self.store:
             raise RuntimeError("the model rebuilt its flat parameter store after this optimizer was created (model moved to another device, or a "
                                "parameter's storage was replaced): the optimizer would update orphaned buffers - build the optimizer after the move")
 
@@ -371,6 +382,8 @@ class FusedCAME(FusedAdamW):
         from .lib import CameTensor, CameTile
         import ctypes as C
         assert model._store is not None, "call model.prepare(device) (or run one forward) before building the optimizer"
+        if getattr(model, "_lora", None) is not None:
+            raise NotImplementedError("FusedCAME on LoRA adapters is not implemented: use FusedAdamW (the reference's LoRA scripts train with AdamW)")
         self.model, self.store = model, model._store
         self.lr, self.betas, self.eps, self.clip, self.wd, self.max_norm = lr, betas, eps, clip_threshold, weight_decay, max_grad_norm
         self.scaler = scaler

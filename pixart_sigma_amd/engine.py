@@ -234,6 +234,11 @@ class Engine:
             D, depth = cfg["hidden_size"], cfg["depth"]
             self._qs = (torch.empty((depth, 3 * D, D), dtype=BF16, device=store.device), torch.empty((depth, 3 * D), dtype=F32, device=store.device))
             store._on_change.append(weakref.WeakMethod(self._refresh_qs))
+        # LoRA adapters (lora.py, attach_lora): None = the plain engine, whose launches are exactly those of tests/golden/engine_schedule_*.txt.  Otherwise the
+        # adapters are folded into the shadow weights (and the prescaled qkv copy) behind every re-cast / optimizer step, the forward and the dX GEMMs run
+        # unchanged on the merged operands, and the backward computes adapter gradients only: the base model is frozen.
+        self.lora = None
+        self._lora_refs = ()
 
     # ------------------------------------------------------------------ helpers
     def pos_table(self, h, w):
@@ -272,13 +277,20 @@ class Engine:
         return ops.gemm(x, self.S.w(name + ".weight"), NT, bias=self.S.f(name + ".bias"), descending=self._desc(name), **kw)
 
     def _lin_bwd(self, dy, x, name, need_dx=True, dx_kw=None, bias_done=False):
-        """dW += dy^T x ; db += colsum(dy) (unless the kernel that produced dy already accumulated it) ; returns dx = dy W (bf16)."""
+        """dW += dy^T x ; db += colsum(dy) (unless the kernel that produced dy already accumulated it) ; returns dx = dy W (bf16).
+        With adapters attached: the base weight and bias are frozen - no TN GEMM, no column sum - and every adapted row slice of the linear gets its
+        dA / dBt from one ops.lora_bwd on x and the slice's column block of dy; dx = dy W_merged is the same GEMM on the merged shadow."""
         S = self.S
-        # (order measured: the weight gradient FIRST - its pass over dy leaves dy in the Infinity Cache for the dX GEMM; dX first is 1.6 ms per step slower,
-        # profiles/r5_20_step_ab_dx_first.txt)
-        ops.gemm(dy, x, TN, out_f32=S.g(name + ".weight"), accumulate=True, split_k=0)
-        if not bias_done:
-            ops.colsum(dy, S.g(name + ".bias"))
+        if self.lora is not None:
+            A = self.lora.store
+            for lo, hi, ad in self.lora.slices.get(name, ()):
+                ops.lora_bwd(x, dy[:, lo:hi], A.w(ad + ".lora_A"), A.w(ad + ".lora_Bt"), self.lora.scale, A.g(ad + ".lora_A"), A.g(ad + ".lora_Bt"))
+        else:
+            # (order measured: the weight gradient FIRST - its pass over dy leaves dy in the Infinity Cache for the dX GEMM; dX first is 1.6 ms per step slower,
+            # profiles/r5_20_step_ab_dx_first.txt)
+            ops.gemm(dy, x, TN, out_f32=S.g(name + ".weight"), accumulate=True, split_k=0)
+            if not bias_done:
+                ops.colsum(dy, S.g(name + ".bias"))
         if need_dx:                 # dX of fc1 follows fc2's dX GEMM (upwards); the text-row and caption-MLP GEMMs are too small to care
             desc = not name.endswith(("mlp.fc1", "kv_linear", "y_proj.fc1", "y_proj.fc2"))
             return ops.gemm(dy, S.w(name + ".weight"), NN, descending=desc, **(dx_kw or {}))
@@ -300,6 +312,46 @@ class Engine:
             ops.scale_copy(S.master[offw[i]:], st if n > 1 else 0, n, D * D, 3 * D * D, ops.Q_PRESCALE, out_bf16=w[i:i + n])
             ops.scale_copy(S.master[offb[i]:], st if n > 1 else 0, n, D, 3 * D, ops.Q_PRESCALE, out_f32=b[i:i + n])
             i += n
+
+    # ------------------------------------------------------------------ LoRA adapters
+    def attach_lora(self, lora):
+        """lora: lora.LoraAdapters with its ParamStore built on this engine's device.  From here on every bump of either store re-merges: the base store's
+        re-cast (refresh_shadow) wipes the merge and is followed by it; an adapter update (optimizer step, re-cast of edited adapters) bumps the base store, so
+        the generation that keys Engine._text_cache moves and the shadow / prescaled copy are rewritten in place under any captured graph."""
+        self.detach_lora(remerge=False)
+        self.lora = lora
+        self._lora_refs = (weakref.WeakMethod(self._lora_merge), weakref.WeakMethod(self._lora_changed))
+        self.S._on_change.append(self._lora_refs[0])          # behind _refresh_qs: the prescaled copy is first rewritten from the master, then its adapted rows merged
+        lora.store._on_change.append(self._lora_refs[1])
+        self.S.bump()
+
+    def detach_lora(self, remerge=True):
+        if self.lora is None:
+            return
+        for lst, ref in ((self.S._on_change, self._lora_refs[0]), (self.lora.store._on_change, self._lora_refs[1])):
+            if ref in lst:
+                lst.remove(ref)
+        self.lora, self._lora_refs = None, ()
+        if remerge:
+            self.S.refresh_shadow(force=True)
+
+    def _lora_changed(self):
+        self.S.bump()
+
+    def _lora_merge(self, into_master=False):
+        """shadow rows <- round16(master + s Bt^T A) for every adapted slice: one launch per slice, reading the fp32 masters of both stores (one rounding)."""
+        S, lo_ = self.S, self.lora
+        D = self.cfg["hidden_size"]
+        for name, slices in lo_.slices.items():
+            l = int(name.split(".")[1])
+            qs = self._qs[0][l] if self._qs is not None and name.endswith("attn.qkv") else None
+            for lo, hi, ad in slices:
+                ops.lora_merge(S.f(name + ".weight"), lo, hi, lo_.store.f(ad + ".lora_A"), lo_.store.f(ad + ".lora_Bt"), lo_.scale, S.w(name + ".weight"),
+                               dst2=qs, mul_rows=(0, D), mul=ops.Q_PRESCALE, dst_f32=S.f(name + ".weight") if into_master else None)
+
+    def _pg(self, name):
+        """Gradient accumulator of a base parameter - or, with adapters attached (the base is frozen), a throw-away buffer for kernels that must write one."""
+        return self.S.g(name) if self.lora is None else torch.empty(self.S.shape[name], dtype=F32, device=self.S.device)
 
     # ------------------------------------------------------------------ caption branch
     def caption_fwd(self, y, row_idx, L, drop, y_null):
@@ -411,10 +463,13 @@ class Engine:
         dev = G.device
         # bias gradients ride along with the kernels that produce the output gradients (no separate column-sum passes); they add
         # into PXA_COLSUM_SLOTS partial rows laid out like this block's bias range of the flat gradient buffer
+        frozen = self.lora is not None                  # adapters attached: no base bias gradient is collected anywhere
         bs, be = S.bias_range(p)
-        part = torch.zeros((ops.COLSUM_SLOTS, be - bs), dtype=F32, device=dev)
+        part = None if frozen else torch.zeros((ops.COLSUM_SLOTS, be - bs), dtype=F32, device=dev)
 
         def pb(name, lo=0, hi=None):
+            if frozen:
+                return None
             o = S.offset[p + name] - bs
             return part[:, o + lo:o + (S.numel[p + name] if hi is None else hi)]
         # ---- MLP branch: x3 = x2 + gate_mlp * u3
@@ -439,7 +494,7 @@ class Engine:
                           kv_start=ctx.kv_start, kv_len=ctx.kv_len, max_kv_len=ctx.max_len, kv_len_host=ctx.lens_host)
         gq = self._lin_bwd(dqc, sv.x1b, p + "cross_attn.q_linear")
         # 4,800 text rows fill 95 of 256 CUs with 256 x 256 tiles: split_k = 0 lets the library's (tile, split) model choose (128 x 128 here: 72us -> 47us)
-        self._lin_bwd(dkvc, ctx.ye, p + "cross_attn.kv_linear", dx_kw=dict(out_f32=ctx.dye, accumulate=True, split_k=0))
+        self._lin_bwd(dkvc, ctx.ye, p + "cross_attn.kv_linear", need_dx=not frozen, dx_kw=dict(out_f32=ctx.dye, accumulate=True, split_k=0))   # frozen caption MLP: nobody reads d(ye)
         # ---- self attention: x1 = x_in + gate_msa * u1 ; G1 = G + gq
         ops.gate_bwd(G, add=gq, u=sv.u1, gate=mod[:, 2], mod_stride=st, dx_out=G, du=du, dgate=dmod[:, 2], dmod_stride=st, rows_per_batch=N,
                      dbias=pb("attn.proj.bias"))
@@ -457,8 +512,8 @@ class Engine:
         if skv.bwd == "compress":
             (hh, ww), sr = ctx.hw, c["kv_scale_factor"]
             cw, cb, lw = S.f(p + "attn.sr.weight"), S.f(p + "attn.sr.bias"), S.f(p + "attn.norm.weight")
-            gcw, gcb = S.g(p + "attn.sr.weight"), S.g(p + "attn.sr.bias")
-            glw, glb = S.g(p + "attn.norm.weight"), S.g(p + "attn.norm.bias")
+            gcw, gcb = self._pg(p + "attn.sr.weight"), self._pg(p + "attn.sr.bias")
+            glw, glb = self._pg(p + "attn.norm.weight"), self._pg(p + "attn.norm.bias")
             for dyc, lo in ((dk, D), (dv, 2 * D)):     # the same sr / norm parameters process K and V (PixArt_blocks.py:138-139)
                 ops.kv_compress_bwd(dyc, qkv[:, lo:lo + D], N * 3 * D, 3 * D, cw, cb, lw, dqkv[:, lo:lo + D], N * 3 * D, 3 * D,
                                     gcw, gcb, glw, glb, B, hh, ww, D, sr)
@@ -468,13 +523,14 @@ class Engine:
             ops.kv_pick(dv, dqkv[:, 2 * D:], N * 3 * D, 3 * D, B, hh, ww, D, sr, backward=True)
         if sv.qkn is not None:                               # back through q_norm / k_norm: dqkv's q, k blocks become d(raw q), d(raw k)
             (qs, qm, qr), (ks_, km, kr) = sv.qkn
-            ops.ln_affine_bwd(dqkv[:, :D], qs, qm, qr, S.f(p + "attn.q_norm.weight"), S.g(p + "attn.q_norm.weight"), S.g(p + "attn.q_norm.bias"))
-            ops.ln_affine_bwd(dqkv[:, D:2 * D], ks_, km, kr, S.f(p + "attn.k_norm.weight"), S.g(p + "attn.k_norm.weight"), S.g(p + "attn.k_norm.bias"))
+            ops.ln_affine_bwd(dqkv[:, :D], qs, qm, qr, S.f(p + "attn.q_norm.weight"), self._pg(p + "attn.q_norm.weight"), self._pg(p + "attn.q_norm.bias"))
+            ops.ln_affine_bwd(dqkv[:, D:2 * D], ks_, km, kr, S.f(p + "attn.k_norm.weight"), self._pg(p + "attn.k_norm.weight"), self._pg(p + "attn.k_norm.bias"))
         # the attention kernels can also emit the q/k/v bias-gradient sums (pxa_attn_args.d*_colsum), but the cross-lane row
         # reductions cost them more (~0.5 ms/block) than one streaming column-sum pass over dqkv (~0.2 ms/block): measured, not used
         dxn = self._lin_bwd(dqkv, sv.xn1, p + "attn.qkv")
         ops.ln_mod_bwd(dxn, sv.x_in, sv.mean1, sv.rstd1, mod[:, 1], st, G, G, dmod[:, 0], dmod[:, 1], st, N)
-        ops.colsum_reduce(part, S.grad[bs:be])
+        if not frozen:
+            ops.colsum_reduce(part, S.grad[bs:be])
         if self.grad_ready_hook:
             self.grad_ready_hook(f"blocks.{l}")
         return G
@@ -547,7 +603,8 @@ class Engine:
         dev = dout.device
         ctx.dmod = torch.zeros_like(ctx.mod)
         dfin = torch.zeros_like(saved.fin_mod)
-        ctx.dye = torch.zeros(ctx.ye.shape, dtype=F32, device=dev)
+        frozen = self.lora is not None                  # adapters attached: the embedders and the final layer are frozen, the blocks' adapters alone get gradients
+        ctx.dye = None if frozen else torch.zeros(ctx.ye.shape, dtype=F32, device=dev)
         dlin = ops.patchify_bwd(dout.contiguous(), h, w)
         dxn = self._lin_bwd(dlin, saved.xnf, "final_layer.linear")
         G = torch.empty((B * N, D), dtype=F32, device=dev)
@@ -561,8 +618,9 @@ class Engine:
                 sv = self._recompute(l, sv, ctx)
             G = self.block_bwd(l, G, sv, ctx)
             saved.blocks[l] = None
-        ops.patch_embed_bwd(saved.x, G, S.g("x_embedder.proj.weight"), S.g("x_embedder.proj.bias"))
-        self.caption_bwd(ctx.dye, saved.cap)
+        if not frozen:
+            ops.patch_embed_bwd(saved.x, G, S.g("x_embedder.proj.weight"), S.g("x_embedder.proj.bias"))
+            self.caption_bwd(ctx.dye, saved.cap)
         return ctx.dmod, dfin
 
     def _recompute(self, l, sv, ctx):

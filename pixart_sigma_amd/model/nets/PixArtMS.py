@@ -174,6 +174,8 @@ class _CoreFn(torch.autograd.Function):
         model, saved = ctx.model, ctx.saved
         ctx.saved = None
         model._store.attach_grads()
+        if model._lora is not None:
+            model._lora.store.attach_grads()
         dmod, dfin = model._engine.backward(dout.to(F32), saved)
         hook = model._engine.grad_ready_hook
         if hook is not None:
@@ -289,6 +291,7 @@ class PixArtMS(nn.Module):
             for i in range(depth)])
         self.final_layer = T2IFinalLayer(hidden_size, patch_size, self.out_channels)
         self._store = self._engine = None
+        self._lora = None                 # lora.LoraAdapters once add_lora / load_lora attached adapters (not a submodule: the base parameter list stays as it is)
         self._anchor = None
         self._mask_cache = {}
         self.initialize()
@@ -380,6 +383,33 @@ class PixArtMS(nn.Module):
             self._engine = Engine(self._store, cfg)
             self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self._store.refresh_shadow()
+        if self._lora is not None:       # behind the base re-cast: the merge reads both fp32 masters and rewrites the adapted rows of the shadow
+            self._lora.prepare(self, device)
+
+    # ---- LoRA adapters (lora.py; the reference's peft calls, train_scripts/train_pixart_lora_hf.py:505-524,552,990)
+    def add_lora(self, config=None, **kw):
+        from ...lora import add_lora
+        return add_lora(self, config, **kw)
+
+    def load_lora(self, path, scale=1.0):
+        from ...lora import load_lora
+        return load_lora(self, path, scale)
+
+    def save_lora(self, path):
+        from ...lora import save_lora
+        return save_lora(self, path)
+
+    def set_lora_scale(self, x):
+        from ...lora import set_lora_scale
+        return set_lora_scale(self, x)
+
+    def merge_and_unload(self):
+        from ...lora import merge_and_unload
+        return merge_and_unload(self)
+
+    def lora_parameters(self):
+        """The adapters' nn.Parameters (empty without adapters)."""
+        return [] if self._lora is None else list(self._lora.params.values())
 
     # ---- forward (PixArtMS.py:165-211)
     def forward(self, x, timestep, y, mask=None, data_info=None, **kwargs):
@@ -428,7 +458,8 @@ class PixArtMS(nn.Module):
             assert tuple(y.shape[2:]) == tuple(self.y_embedder.y_embedding.shape)       # PixArt_blocks.py:401-402
             if self.y_embedder.uncond_prob > 0:                                         # token_drop, PixArt_blocks.py:389-398 (CPU RNG draw)
                 drop = (torch.rand(bs) < self.y_embedder.uncond_prob).to(device=dev, dtype=torch.int32)
-        anchor = self._anchor if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) else None
+        trainable = any(p.requires_grad for p in self.parameters()) or (self._lora is not None and self._lora.trainable)
+        anchor = self._anchor if torch.is_grad_enabled() and trainable else None
         return _CoreFn.apply(self, x, y2d, mod, fin, row_idx, lens, drop, anchor)
 
     def forward_with_dpmsolver(self, x, timestep, y, data_info, **kwargs):

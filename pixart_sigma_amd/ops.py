@@ -420,6 +420,53 @@ def cast_bf16(x, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ LoRA adapters
+LORA_MAX_RANK = 64
+_LORA_WS = {}
+
+
+def lora_merge(master, lo, hi, A, Bt, s, dst, dst2=None, mul_rows=(0, 0), mul=1.0, dst_f32=None):
+    """Rows [lo, hi) of dst <- round16(master + s * Bt^T A) (pxa_lora_merge): master (rows, K) fp32, dst its 16-bit copy (same rows), A (r, K) and
+    Bt (r, hi - lo) fp32.  dst2: optional second 16-bit copy whose rows in mul_rows carry `mul` (the q-prescaled qkv copy); dst_f32: optional fp32
+    destination laid out as master (master itself: merge_and_unload)."""
+    _chk(master, F32, "master"); _chk(A, F32, "A"); _chk(Bt, F32, "Bt"); _chk(dst, BF16, "dst")
+    r, K = A.shape
+    assert master.dim() == 2 and master.shape[1] == K and tuple(dst.shape) == tuple(master.shape) and 0 <= lo < hi <= master.shape[0]
+    assert tuple(Bt.shape) == (r, hi - lo) and A.is_contiguous(), "lora_merge: A (r, K) contiguous, Bt (r, hi - lo)"
+    if dst2 is not None:
+        _chk(dst2, BF16, "dst2")
+        assert tuple(dst2.shape) == tuple(master.shape)
+    if dst_f32 is not None:
+        _chk(dst_f32, F32, "dst_f32")
+        assert tuple(dst_f32.shape) == tuple(master.shape) and dst_f32.stride(0) == master.stride(0)
+    call("pxa_lora_merge", ptr(master), master.stride(0), lo, hi, K, ptr(A), ptr(Bt), Bt.stride(0), r, float(s), ptr(dst), dst.stride(0),
+         ptr(dst2), dst2.stride(0) if dst2 is not None else 0, int(mul_rows[0]), int(mul_rows[1]), float(mul), ptr(dst_f32))
+
+
+def lora_bwd(x, dy, A16, Bt16, s, dA, dBt):
+    """dA += s u^T x, dBt += s t^T dy with t = x A16^T, u = dy Bt16^T rounded once to the operand type (pxa_lora_bwd).  x (M, K), dy (M, N) 16-bit with unit
+    column stride (dy may be a column block of a wider matrix); A16 (r, K), Bt16 (r, N) the adapters' 16-bit copies; dA (r, K), dBt (r, N) fp32.  The workspace
+    is cached per (device, stream): the call's kernels run on one stream and the last one has read it before the next call's first writes."""
+    for name, t in (("x", x), ("dy", dy), ("A16", A16), ("Bt16", Bt16)):
+        _chk(t, BF16, name)
+    _chk(dA, F32, "dA"); _chk(dBt, F32, "dBt")
+    M, K = x.shape
+    N, r = dy.shape[1], A16.shape[0]
+    assert dy.shape[0] == M and tuple(A16.shape) == (r, K) and tuple(Bt16.shape) == (r, N) and tuple(dA.shape) == (r, K) and tuple(dBt.shape) == (r, N)
+    assert A16.is_contiguous() and Bt16.is_contiguous() and dA.is_contiguous() and dBt.is_contiguous()
+    need = lib.load().pxa_lora_bwd_ws_bytes(M, K, N, r)
+    if need < 0:
+        raise lib.PixartHipError(f"pxa_lora_bwd: no workspace size for M={M}, K={K}, N={N}, r={r} (1 <= r <= {LORA_MAX_RANK})")
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    else:
+        key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
+        ws = _LORA_WS.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _LORA_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    call("pxa_lora_bwd", ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(A16), ptr(Bt16), M, K, N, r, float(s), ptr(dA), ptr(dBt), ptr(ws), ws.numel())
+
+
 # ------------------------------------------------------------------------------------------------ VAE conv stack
 class Grid:
     """A bf16 NHWC pixel grid (pxa_grid): pixel (b, y, x) is the C-vector at buf[(b*img_pitch + y*row_pitch + x + origin) * C]."""

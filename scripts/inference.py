@@ -54,6 +54,8 @@ def get_args():
     p.add_argument("--t5_path", default=None, type=str, help="transformers T5 directory (weights + tokenizer): encode the prompts with the in-repo T5 encoder first")
     p.add_argument("--t5_timeout", default=1800, type=int, help="seconds the T5 child process may take")
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
+    p.add_argument("--lora_path", default=None, type=str, help="peft-format adapter directory (adapter_config.json + adapter_model.safetensors) for the transformer blocks")
+    p.add_argument("--lora_scale", default=1.0, type=float, help="multiplies the adapters' lora_alpha / r (0 = the base model)")
     return p.parse_args()
 
 
@@ -115,6 +117,9 @@ def main():
     if args.model_path:
         sd = torch.load(args.model_path, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd), strict=False)
+    if args.lora_path:                  # folded into the 16-bit operand weights when the model is prepared: the sampler runs the unchanged kernels
+        lo = model.load_lora(args.lora_path, scale=args.lora_scale)
+        print(f"LoRA adapters from {args.lora_path}: r={lo.config.r}, s={lo.scale:g}, {len(lo.params) // 2} adapted linears")
     model = model.to(dev).eval()
     from pixart_sigma_amd.vae import AutoencoderKL
     vae_dir = "output/pretrained_models/sd-vae-ft-ema" if args.sdvae else f"{args.pipeline_load_from}/vae"    # reference inference.py:191-196
