@@ -80,6 +80,20 @@ def test_f16_operand_build_gradient_gemm_and_row_kernel_forms():
     assert "skipped" not in tail, tail
 
 
+@pytest.mark.gpu
+def test_f16_operand_build_came_forms():
+    """tests/test_came_forms_gpu.py re-run against libpixart_hip_f16.so: the optimizer's fp32 states per element as under bf16, and the 16-bit shadow - fp16 there -
+    bit-equal to the parameters cast once."""
+    env = dict(os.environ, PXA_OPERAND_DTYPE="f16")
+    env.pop("PXA_LIB_PATH", None)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_came_forms_gpu.py"), "-q", "-m", "gpu", "-s", "-p", "no:cacheprovider"],
+                       capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+    tail = "\n".join(l for l in r.stdout.splitlines() if ("passed" in l or "failed" in l or "FAILED" in l or "Error" in l))
+    print("\n[f16 build] " + tail.replace("\n", "\n[f16 build] "))
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert "skipped" not in tail, tail
+
+
 F16_VAE_TOL = 4e-3        # measured 1.5e-3 ... 2.0e-3 (bf16 build: 1.2e-2 ... 1.7e-2); the reference runs this network in fp16
 
 
