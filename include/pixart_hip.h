@@ -396,6 +396,29 @@ long pxa_lora_bwd_ws_bytes(long M, int K, int N, int r);
 int pxa_lora_bwd(const void* x, long ldx, const void* dy, long lddy, const void* A16, const void* Bt16, long M, int K, int N, int r, float s, float* dA,
                  float* dBt, void* ws, long ws_bytes, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- Images
+ * The reference's image transforms (tools/extract_features.py:103-111, 216-225; diffusion/data/datasets/InternalData_ms.py:145-155): img.convert('RGB'),
+ * T.Resize (PIL Image.resize: Pillow's 8-bit fixed-point separable resampler), T.CenterCrop, T.ToTensor, T.Normalize([.5], [.5]) - and, on the way out,
+ * torchvision.utils.save_image(normalize=True, value_range=(-1, 1)) (scripts/inference.py:137).
+ *
+ * pxa_image_resample: one uint8 HWC RGB image src (h rows of w pixels, row pitch src_pitch bytes) -> the window [cy, cy + ch) x [cx, cx + cw) of the image resized
+ * to Hr x Wr, byte for byte what Image.resize followed by the crop gives.  Per axis the host supplies Pillow's tables (int32, 22 fractional bits): bounds
+ * [out][2] = (first source index, tap count n) and coefficients - hk TAP-major [hksize][Wr] (coefficient t of output x at hk[t * Wr + x]), vk row-major
+ * [Hr][vksize].  NULL tables for an axis = that pass is skipped (then Wr == w / Hr == h must hold).  The horizontal pass runs first over source rows
+ * [row0, row0 + rows), the rows the window's vertical taps reach: row0 = vb[cy][0], row0 + rows = vb[cy + ch - 1][0] + vb[cy + ch - 1][1] (ignored without a
+ * vertical pass), and writes the uint8 intermediate into ws (pxa_image_resample_ws_bytes(rows, cw) bytes; needed only when both passes run).  Tap counts and
+ * indices are clamped to the table row length and the source, so no table content makes a kernel read out of bounds.
+ * Output, exactly one of: out_f32 = slot of a (B, 3, ch, cw) fp32 tensor (planes of ch * cw floats) receiving lut[byte], lut = 256 fp32 values in device
+ * memory (the caller's (u / 255 - 0.5) / 0.5, computed where its reference computes it); out_u8 = uint8 HWC with row pitch out_pitch bytes.
+ *
+ * pxa_image_to_u8: x (B, 3, H, W) fp32 (is_f16 = 0) or IEEE half (is_f16 = 1, in both operand builds) -> out_u8 (B, H, W, 3):
+ * trunc(clamp((clamp(x, -1, 1) + 1) / 2 * 255 + 0.5, 0, 255)), every step rounded to fp32 (the reference does them in the tensor's own dtype). */
+long pxa_image_resample_ws_bytes(int rows, int cw);
+int pxa_image_resample(const void* src, long src_pitch, int h, int w, const int* hk, const int* hb, int hksize, int Wr, const int* vk, const int* vb, int vksize,
+                       int Hr, int cy, int cx, int ch, int cw, int row0, int rows, void* ws, long ws_bytes, float* out_f32, const float* lut, void* out_u8,
+                       long out_pitch, hipStream_t stream);
+int pxa_image_to_u8(const void* x, int is_f16, long B, int H, int W, void* out_u8, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------- measurement
  * The part's matrix rate under its power limit, for the `roofline` object of bench.py (no reference counterpart: the reference reports no roofline).
  * One launch = `iters` x 32 v_mfma_f32_32x32x16 (shape 32) or 64 v_mfma_f32_16x16x32 (shape 16) per wave on register-resident operand data, one wave per

@@ -467,6 +467,75 @@ def lora_bwd(x, dy, A16, Bt16, s, dA, dBt):
     call("pxa_lora_bwd", ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(A16), ptr(Bt16), M, K, N, r, float(s), ptr(dA), ptr(dBt), ptr(ws), ws.numel())
 
 
+# ------------------------------------------------------------------------------------------------ images
+U8, I32 = torch.uint8, torch.int32
+
+
+def image_resample(src, resized, window, out, htab=None, vtab=None, rows=None, lut=None, ws=None):
+    """The window (cy, cx, ch, cw) of `src` resized to resized = (Hr, Wr) by Pillow's 8-bit resampler (pxa_image_resample).  src: uint8 (h, w, 3), pixels
+    contiguous, any row pitch >= 3 w.  htab = (coefficients int32 (ksize, Wr) tap-major, bounds int32 (Wr, 2)) or None when Wr == w; vtab = (coefficients int32
+    (Hr, ksize), bounds int32 (Hr, 2)) or None when Hr == h; rows = (row0, count), the source rows the window's vertical taps reach (with vtab).  out: an fp32
+    (3, ch, cw) contiguous slot of a batch (needs lut, the 256 fp32 values a byte maps to) or a uint8 (ch, cw, 3) view with any row pitch.  ws: uint8 workspace
+    for the intermediate image, allocated here when both passes run and none is given.  Returns out."""
+    assert src.is_cuda and src.dtype == U8 and src.dim() == 3 and src.shape[2] == 3 and src.stride(2) == 1 and src.stride(1) == 3, "src: uint8 (h, w, 3) on the GPU"
+    h, w = src.shape[:2]
+    Hr, Wr = (int(v) for v in resized)
+    cy, cx, ch, cw = (int(v) for v in window)
+    assert src.stride(0) >= 3 * w and 0 <= cy and 0 <= cx and ch >= 1 and cw >= 1 and cy + ch <= Hr and cx + cw <= Wr, "window outside the resized image"
+    hk = hb = vk = vb = None
+    hks = vks = 0
+    if htab is not None:
+        hk, hb = htab
+        _chk(hk, I32, "htab coefficients"); _chk(hb, I32, "htab bounds")
+        hks = hk.shape[0]
+        assert hk.is_contiguous() and hb.is_contiguous() and tuple(hk.shape) == (hks, Wr) and tuple(hb.shape) == (Wr, 2), "htab: (ksize, Wr) and (Wr, 2)"
+    else:
+        assert Wr == w, "no horizontal tables: the width must not change"
+    row0, nrows = cy, ch
+    if vtab is not None:
+        vk, vb = vtab
+        _chk(vk, I32, "vtab coefficients"); _chk(vb, I32, "vtab bounds")
+        vks = vk.shape[1]
+        assert vk.is_contiguous() and vb.is_contiguous() and tuple(vk.shape) == (Hr, vks) and tuple(vb.shape) == (Hr, 2), "vtab: (Hr, ksize) and (Hr, 2)"
+        assert rows is not None, "vtab needs rows = (first source row, count)"
+        row0, nrows = (int(v) for v in rows)
+        assert 0 <= row0 and nrows >= 1 and row0 + nrows <= h, "rows outside the source"
+    else:
+        assert Hr == h, "no vertical tables: the height must not change"
+    need = 0
+    if htab is not None and vtab is not None:
+        need = lib.load().pxa_image_resample_ws_bytes(nrows, cw)
+        if ws is None:
+            ws = torch.empty(need, dtype=U8, device=src.device)
+        assert ws.is_cuda and ws.dtype == U8 and ws.is_contiguous() and ws.numel() >= need, f"ws: {need} uint8 on the GPU"
+    out_f32 = out_u8 = None
+    pitch = 0
+    if out.dtype == F32:
+        assert out.is_cuda and tuple(out.shape) == (3, ch, cw) and out.is_contiguous(), "out: fp32 (3, ch, cw) contiguous"
+        assert lut is not None and lut.is_cuda and lut.dtype == F32 and lut.numel() == 256 and lut.is_contiguous(), "fp32 output needs the 256-entry table"
+        out_f32 = out
+    else:
+        assert out.is_cuda and out.dtype == U8 and tuple(out.shape) == (ch, cw, 3) and out.stride(2) == 1 and out.stride(1) == 3 and out.stride(0) >= 3 * cw, \
+            "out: uint8 (ch, cw, 3), pixels contiguous"
+        out_u8, pitch = out, out.stride(0)
+    call("pxa_image_resample", ptr(src), src.stride(0), h, w, ptr(hk), ptr(hb), hks, Wr, ptr(vk), ptr(vb), vks, Hr, cy, cx, ch, cw, row0, nrows,
+         ptr(ws) if need else None, ws.numel() if need else 0, ptr(out_f32), ptr(lut) if out_f32 is not None else None, ptr(out_u8), pitch)
+    return out
+
+
+def image_to_u8(x, out=None):
+    """(B, 3, H, W) fp16 / fp32 in [-1, 1] -> uint8 (B, H, W, 3): torchvision.utils.save_image(normalize=True, value_range=(-1, 1))'s
+    clamp, (x + 1) / 2, * 255 + 0.5, clamp, truncate (pxa_image_to_u8).  The arithmetic is fp32 whatever the input type; the reference does it in the tensor's own
+    dtype, so an fp16 input can differ from it by one step where the fp16 product rounds across an integer."""
+    assert x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.dtype in (torch.float16, F32) and x.is_contiguous(), "x: (B, 3, H, W) fp16 / fp32 contiguous on the GPU"
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=U8, device=x.device)
+    assert out.is_cuda and out.dtype == U8 and tuple(out.shape) == (B, H, W, 3) and out.is_contiguous()
+    call("pxa_image_to_u8", ptr(x), int(x.dtype == torch.float16), B, H, W, ptr(out))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ VAE conv stack
 class Grid:
     """A bf16 NHWC pixel grid (pxa_grid): pixel (b, y, x) is the C-vector at buf[(b*img_pitch + y*row_pitch + x + origin) * C]."""

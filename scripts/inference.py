@@ -56,6 +56,7 @@ def get_args():
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
     p.add_argument("--lora_path", default=None, type=str, help="peft-format adapter directory (adapter_config.json + adapter_model.safetensors) for the transformer blocks")
     p.add_argument("--lora_scale", default=1.0, type=float, help="multiplies the adapters' lora_alpha / r (0 = the base model)")
+    p.add_argument("--save_images", default=None, choices=["png", "jpg"], help="also write one picture per sample (as the reference's save_image: output/<save_name>/<index>.<ext>)")
     return p.parse_args()
 
 
@@ -152,6 +153,10 @@ def main():
         if vae is not None:
             imgs = vae.decode(samples.half() / vae.config.scaling_factor).sample
             torch.save(imgs.cpu(), os.path.join("output", args.save_name, f"images_{start}.pt"))
+            if args.save_images:                                     # reference inference.py:137: save_image(normalize=True, value_range=(-1, 1))
+                from pixart_sigma_amd.data.images import save_png
+                for i in range(n):
+                    save_png(imgs[i], os.path.join("output", args.save_name, f"{start + i}.{args.save_images}"))
         else:
             torch.save(samples.cpu(), os.path.join("output", args.save_name, f"latents_{start}.pt"))
         print(f"[{start}:{start + n}] sampled {tuple(samples.shape)} in {steps} steps")
