@@ -1,4 +1,4 @@
-"""The VALUES of every launched call of tools/gemm_dispatch.py:CASES, under every dispatch knob: what the kernel that launch_instance's switch launches
+"""The VALUES of every launched call of tools/gemm_dispatch.py:ALL_CASES, under every dispatch knob: what the kernel that launch_instance's switch launches
 (csrc/gemm.hip, gemm_nt4.hip) wrote, against gd.reference() - plain torch in fp64 from the 16-bit-rounded operands.  tests/test_gemm_plan.py pins which
 instance the plan NAMES, on CPU tensors; here the same plan line is asserted beside the numbers, so a value belongs to the instance named.
 
@@ -16,14 +16,18 @@ specified.  Bounds, from the project and not from the kernels under test:
   fp32 outputs          2e-5 (test_gemm_tn_splitk_accumulate: K = 4096, split 8);
   column sums           1e-4 against the sums of the stored 16-bit values, 5e-3 against the reference's (test_gemm_persistent_kernel_epilogues);
   gn_part               what check_statistics of tests/test_vae_conv_geometry_gpu.py asserts.
-The reference alone, rounded once to the type of the output and held against itself with the same figures on the CPU, over all 57 cases (worst block):
-16-bit outputs 1.83e-3 (out, conv_phase_128) and 2.06e-3 (out2 = GELU', nt_gelu_save_grad) of the 4e-3 with bf16 operands, 2.24e-4 and 2.44e-4 of the 5e-4
-with fp16 operands; fp32 outputs 2.7e-8 of the 2e-5; column sums of the rounded values against the reference's 2.48e-3 (bf16) / 2.7e-4 (fp16) of the 5e-3,
-against the stored values 3e-8 of the 1e-4.  No case's reference alone uses more than 52 % of its bound, so no bound is widened.
+The reference alone, rounded once to the type of the output and held against itself with the same figures on the CPU, over all 64 cases, the seven T5 forms
+included (worst block): 16-bit outputs 1.84e-3 (out, t5_gelu_no_bias) and 2.06e-3 (out2 = GELU', nt_gelu_save_grad) of the 4e-3 with bf16 operands, 2.26e-4
+and 2.44e-4 of the 5e-4 with fp16 operands; fp32 outputs 2.8e-8 (t5_residual_900_rows) of the 2e-5; column sums of the rounded values against the reference's
+2.48e-3 (bf16) / 2.7e-4 (fp16) of the 5e-3, against the stored values 3e-8 of the 1e-4.  No case's reference alone uses more than 52 % of its bound (the T5
+cases: 46 %), so no bound is widened.  The T5 forms on an MI355X, worst block over the 13 settings (bf16 operands): t5_qkv_1120_rows 1.73e-3, t5_gelu_no_bias
+1.84e-3, t5_mul_aux 1.83e-3, t5_mul_aux_1152 1.79e-3 - the reference's own rounding - and the fp32 residuals t5_residual_1024 5.3e-8, t5_residual_k320 7.9e-8,
+t5_residual_900_rows 7.8e-8.
 What reading the kernels for this list found: the LDS-staged epilogue of gemm_glds_kernel summed the column sums from the fp32 values BEFORE they were rounded
 (about 1e-3 from the sums of the stored bf16 values, ten times the 1e-4), where the persistent kernel and the separate pass sum what is stored, as
 include/pixart_hip.h says; it now sums the packed values (cases nt_small_colsum and, under the tile / no_persistent knobs, every colsum case).
-test_the_checker_has_teeth (CPU) feeds the comparison a correct rounded result and five defective ones."""
+test_the_checker_has_teeth (CPU) feeds the comparison a correct rounded result and eight defective ones, three of them in the T5 encoder's forms (the fp32
+residual overwritten, its last 32 rows added twice, x aux of the ragged tile one row off)."""
 import json
 import os
 import subprocess
@@ -41,9 +45,10 @@ import gemm_dispatch as gd  # noqa: E402
 OWN_SETTINGS = {"ascending": {"PXA_GEMM_ASCENDING": "1"}, "static_items": {"PXA_GEMM_STATIC": "1"}, "dynamic_items": {"PXA_GEMM_DYNAMIC": "1"}}
 ALL_SETTINGS = {**gd.SETTINGS, **OWN_SETTINGS}
 F32_TOL, COLSUM_STORED_TOL, COLSUM_REFERENCE_TOL = 2e-5, 1e-4, 5e-3
-CHILD_TIMEOUT = 300        # seconds.  PROVISIONAL: meant to be three times the measured wall time of the slowest setting's child (process start and library load
-#                            dominate and vary); no child has been timed on a GPU yet - each test records its child's wall time with record_parity, set it from those
-LAUNCHED = [n for n, s in gd.CASES if "refused" not in s]
+CHILD_TIMEOUT = 12         # seconds: three times the measured wall time of the slowest setting's child (process start and library load dominate and vary).  On an
+#                            MI355X the 13 children of the 64-case list took 3.1 - 3.8 s (the first one started, `default`, 3.8 s), the children of the 57-case list
+#                            before the T5 forms 2.8 - 3.5 s; each test records its child's wall time with record_parity
+LAUNCHED = [n for n, s in gd.ALL_CASES if "refused" not in s]
 _STOP = []                 # why no further child is started
 
 
@@ -91,7 +96,7 @@ def test_call_list_values(setting):
     cases = got["cases"]
     assert list(cases) == LAUNCHED, set(LAUNCHED) ^ set(cases)                                   # a silently skipped case fails
     want = tgp.expected(setting if setting in tgp.CHANGED else "default")                        # nt4 and the three of this file: the default plans
-    specs, bad, worst = dict(gd.CASES), [], {}
+    specs, bad, worst = dict(gd.ALL_CASES), [], {}
     print(f"\n[{setting}] child wall time {wall:.1f} s")
     for name, c in cases.items():
         if want[name][0] == "refused":
@@ -115,7 +120,7 @@ def test_the_checker_has_teeth():
     accumulate; the convolutions against a second statement of them - the segmented A operand gathered, times B, row by row, scattered for the phase case - which also
     pins reference()'s conv2d geometry), and each of five defects fails at the figure it should."""
     from pixart_sigma_amd import ops
-    specs = dict(gd.CASES)
+    specs = dict(gd.ALL_CASES)
 
     def call(name):
         spec = specs[name]
@@ -136,7 +141,8 @@ def test_the_checker_has_teeth():
         return misses(name, spec, gd.errors(spec, kw, ref, statistics=False), [k for k in gd.written(spec) if not k.startswith("gn_")])
 
     # clean results pass
-    for name in ("nt_plain_1152", "nt_gelu_save_grad", "nt_gelu_out2", "nn_mul_aux_colsum_1152", "nt_small_colsum", "tn_accumulate_one_slice", "tn_bias", "nt_small_f32"):
+    for name in ("nt_plain_1152", "nt_gelu_save_grad", "nt_gelu_out2", "nn_mul_aux_colsum_1152", "nt_small_colsum", "tn_accumulate_one_slice", "tn_bias", "nt_small_f32",
+                 "t5_residual_1024", "t5_mul_aux"):
         spec, a, b, kw, ref = call(name)
         store(kw, ref)
         assert verdict(name, spec, kw, ref) == [], name
@@ -195,18 +201,33 @@ def test_the_checker_has_teeth():
     got = verdict("nt_small_colsum", spec, kw, ref)
     assert got and all(": colsum_to_stored " in m for m in got), got
 
-    def overwritten(r, held=None):
-        spec, a, b, kw, _ = call("tn_accumulate_one_slice")
-        r["out_f32"] -= kw["out_f32"].double()
+    def overwritten(name):
+        def edit(r):
+            spec, a, b, kw, _ = call(name)
+            r["out_f32"] -= kw["out_f32"].double()
+            return r
+        return edit
+    fails("tn_accumulate_one_slice", overwritten("tn_accumulate_one_slice"), "out_f32")
+    fails("t5_residual_1024", overwritten("t5_residual_1024"), "out_f32")                       # the encoder's residual stream, stored where it is added into
+
+    def last_wave_row_adds_twice(r):
+        spec, a, b, kw, _ = call("t5_residual_1024")
+        r["out_f32"][1088:] += r["out_f32"][1088:] - kw["out_f32"].double()[1088:]               # the 32 rows of the ragged tile's last wave tile
         return r
-    fails("tn_accumulate_one_slice", overwritten, "out_f32")
+    fails("t5_residual_1024", last_wave_row_adds_twice, "out_f32")
+
+    def aux_of_the_row_before(r):
+        spec, a, b, kw, _ = call("t5_mul_aux")
+        r["out"][1024:] = (a.double() @ b.double().t())[1024:] * kw["aux"].double()[1023:-1]    # the ragged last tile reads its aux rows one row off
+        return r
+    fails("t5_mul_aux", aux_of_the_row_before, "out")
 
 
 if __name__ == "__main__":                                             # the child of test_call_list_values: the list once, in this process's environment
     from pixart_sigma_amd import ops
     from pixart_sigma_amd.lib import PixartHipError
     cases = {}
-    for i, (name, spec) in enumerate(gd.CASES):
+    for i, (name, spec) in enumerate(gd.ALL_CASES):
         if "refused" in spec:
             continue
         try:

@@ -6,7 +6,13 @@ The expected lines are meant to be the parent commit's behaviour.  So far they r
 comparison that is to establish them on a GPU (tools/gemm_dispatch.py under rocprofv3 --kernel-trace at both commits, --check against these plan lines) has not
 been run yet.  They additionally rest on values: tests/test_gemm_call_list_gpu.py runs every launched call on the GPU under each setting (default, no_persistent,
 no_half_items, no_staged_epilogue, seg_half, tile_128, tile_256x128, tile_256, no_glds, nt4, and ascending / static_items / dynamic_items with the default
-plans), asserts expected() on the plan line of the very call and compares what the kernel wrote with an fp64 reference."""
+plans), asserts expected() on the plan line of the very call and compares what the kernel wrote with an fp64 reference.
+
+The seven t5_* cases (the T5 encoder's forms, added after the dispatch was pinned) were taken from ops.gemm_plan of the unchanged library and confirmed against
+choose_gemm by reading: bf16-only NT at M, N >= 1024 is the persistent kernel (PLAIN; GELU for act 1 with one output and no remainder column; GENERIC for act
+4 without column sums, which carries no remainder mode of its own, so PXA_GEMM_NO_HALF_ITEMS changes nothing at N = 1152); an fp32 output is never the
+persistent kernel for NT, so the residual takes the two-stage kernel's direct epilogue at the tile the row count or PXA_GEMM_TILE gives, and split 1 makes the
+accumulate mode 2."""
 import json
 import os
 import subprocess
@@ -78,6 +84,13 @@ DEFAULT = {
     "conv_768_rows":            ("gemm_glds_kernel<0,128,128,2,2,1,true>", 1, 576, 0, ""),
     "conv_res_768_rows":        ("gemm_glds_kernel<0,128,128,2,2,0,true>", 1, 576, 0, ""),
     "conv_f32":                 ("gemm_glds_kernel<0,128,128,2,2,0,true>", 1, 576, 0, ""),
+    "t5_qkv_1120_rows":         ("gemm_pers_kernel<0,0,0,false>", 1, 128, 0, "n"),
+    "t5_gelu_no_bias":          ("gemm_pers_kernel<0,7,0,false>", 1, 128, 0, ""),
+    "t5_mul_aux":               ("gemm_pers_kernel<0,3,0,false>", 1, 128, 0, ""),
+    "t5_mul_aux_1152":          ("gemm_pers_kernel<0,3,0,false>", 1, 128, 0, ""),
+    "t5_residual_1024":         ("gemm_glds_kernel<0,256,256,2,4,0,false>", 1, 128, 2, ""),
+    "t5_residual_k320":         ("gemm_glds_kernel<0,256,256,2,4,0,false>", 1, 320, 2, ""),
+    "t5_residual_900_rows":     ("gemm_glds_kernel<0,128,128,2,2,0,false>", 1, 320, 2, ""),
 }
 # setting -> the cases whose plan differs from DEFAULT: (kernel instance, flags), or ("refused", message); split, k_per_split and the accumulate mode never
 # depend on a knob
@@ -119,6 +132,10 @@ CHANGED = {
         "conv_res_stats_256":       ("refused", "gn_part needs the persistent implicit-convolution path"),
         "conv_res_stats_384":       ("refused", "gn_part needs the persistent implicit-convolution path"),
         "conv_phase_128":           ("refused", "gn_part needs the persistent implicit-convolution path"),
+        "t5_qkv_1120_rows":         ("gemm_glds_kernel<0,256,256,2,4,1,false>", ""),
+        "t5_gelu_no_bias":          ("gemm_glds_kernel<0,256,256,2,4,1,false>", ""),
+        "t5_mul_aux":               ("gemm_glds_kernel<0,256,256,2,4,1,false>", ""),
+        "t5_mul_aux_1152":          ("gemm_glds_kernel<0,256,256,2,4,1,false>", ""),
     },
     "no_half_items": {
         "nt_plain_1152":            ("gemm_pers_kernel<0,0,0,false>", "n"),
@@ -169,6 +186,12 @@ CHANGED = {
         "tn_split_17_atomics":      ("gemm_glds_kernel<2,128,128,2,2,0,false>", ""),
         "tn_cost_model_4608_rows":  ("gemm_glds_kernel<2,128,128,2,2,0,false>", "r"),
         "tn_bias":                  ("gemm_glds_kernel<2,128,128,2,2,0,false>", ""),
+        "t5_qkv_1120_rows":         ("gemm_glds_kernel<0,128,128,2,2,1,false>", ""),
+        "t5_gelu_no_bias":          ("gemm_glds_kernel<0,128,128,2,2,1,false>", ""),
+        "t5_mul_aux":               ("gemm_glds_kernel<0,128,128,2,2,1,false>", ""),
+        "t5_mul_aux_1152":          ("gemm_glds_kernel<0,128,128,2,2,1,false>", ""),
+        "t5_residual_1024":         ("gemm_glds_kernel<0,128,128,2,2,0,false>", ""),
+        "t5_residual_k320":         ("gemm_glds_kernel<0,128,128,2,2,0,false>", ""),
     },
     "tile_256x128": {
         "nt_plain_1024":            ("gemm_glds_kernel<0,256,128,4,2,1,false>", ""),
@@ -207,6 +230,13 @@ CHANGED = {
         "tn_cost_model_4608_rows":  ("gemm_glds_kernel<2,256,128,4,2,0,false>", "r"),
         "tn_bias":                  ("gemm_glds_kernel<2,256,128,4,2,0,false>", ""),
         "nn_f32_accumulate":        ("gemm_glds_kernel<1,256,128,4,2,0,false>", "r"),
+        "t5_qkv_1120_rows":         ("gemm_glds_kernel<0,256,128,4,2,1,false>", ""),
+        "t5_gelu_no_bias":          ("gemm_glds_kernel<0,256,128,4,2,1,false>", ""),
+        "t5_mul_aux":               ("gemm_glds_kernel<0,256,128,4,2,1,false>", ""),
+        "t5_mul_aux_1152":          ("gemm_glds_kernel<0,256,128,4,2,1,false>", ""),
+        "t5_residual_1024":         ("gemm_glds_kernel<0,256,128,4,2,0,false>", ""),
+        "t5_residual_k320":         ("gemm_glds_kernel<0,256,128,4,2,0,false>", ""),
+        "t5_residual_900_rows":     ("gemm_glds_kernel<0,256,128,4,2,0,false>", ""),
     },
     "tile_256": {
         "nt_small":                 ("gemm_pers_kernel<0,0,0,false>", "n"),
@@ -220,6 +250,7 @@ CHANGED = {
         "tn_cost_model_1024":       ("gemm_pers_kernel<2,0,0,false>", "r"),
         "tn_cost_model_32_rows":    ("gemm_pers_kernel<2,0,1,false>", "r"),
         "nn_f32_accumulate":        ("gemm_glds_kernel<1,256,256,2,4,0,false>", "r"),
+        "t5_residual_900_rows":     ("gemm_glds_kernel<0,256,256,2,4,0,false>", ""),
     },
     "no_glds": {
         "nt_plain_1024":            ("gemm_kernel<0>", ""),
@@ -258,6 +289,13 @@ CHANGED = {
         "tn_cost_model_4608_rows":  ("gemm_kernel<2>", "r"),
         "tn_bias":                  ("gemm_kernel<2>", ""),
         "nn_f32_accumulate":        ("gemm_kernel<1>", "r"),
+        "t5_qkv_1120_rows":         ("gemm_kernel<0>", ""),
+        "t5_gelu_no_bias":          ("gemm_kernel<0>", ""),
+        "t5_mul_aux":               ("gemm_kernel<0>", ""),
+        "t5_mul_aux_1152":          ("gemm_kernel<0>", ""),
+        "t5_residual_1024":         ("gemm_kernel<0>", ""),
+        "t5_residual_k320":         ("gemm_kernel<0>", ""),
+        "t5_residual_900_rows":     ("gemm_kernel<0>", ""),
     },
 }
 
@@ -275,7 +313,7 @@ def plans_of_this_process():
     from pixart_sigma_amd import ops
     from pixart_sigma_amd.lib import PixartHipError
     out = {}
-    for i, (name, spec) in enumerate(gd.CASES):
+    for i, (name, spec) in enumerate(gd.ALL_CASES):
         a, b, kw = gd.make_call(spec, "cpu", values=False)
         try:
             out[name] = plan_fields(ops.gemm_plan(a, b, **kw))
@@ -288,7 +326,7 @@ def expected(setting):
     want = dict(DEFAULT)
     for name, v in CHANGED.get(setting, {}).items():
         want[name] = v if v[0] == "refused" else (v[0], *DEFAULT[name][1:4], v[1])
-    for name, spec in gd.CASES:
+    for name, spec in gd.ALL_CASES:
         if "refused" in spec:
             want[name] = ("refused", spec["refused"])
     return want
@@ -296,7 +334,7 @@ def expected(setting):
 
 def assert_plans(got, setting):
     want = expected(setting)
-    assert list(got) == [n for n, _ in gd.CASES] and set(want) == set(got)
+    assert list(got) == [n for n, _ in gd.ALL_CASES] and set(want) == set(got)
     for name, w in want.items():
         if w[0] == "refused":
             assert got[name][0] == "refused" and "pxa_gemm_plan failed (rc=-1): pxa_gemm: " + w[1] in got[name][1], (setting, name, got[name])
@@ -305,7 +343,7 @@ def assert_plans(got, setting):
 
 
 def test_tables_cover_the_call_list():
-    launched = [n for n, s in gd.CASES if "refused" not in s]
+    launched = [n for n, s in gd.ALL_CASES if "refused" not in s]
     assert list(DEFAULT) == launched and len(set(launched)) == len(launched)
     assert set(CHANGED) | {"default", "nt4"} == set(gd.SETTINGS)
     for setting, rows in CHANGED.items():

@@ -43,6 +43,47 @@ def test_bucket_port_equals_transformers(key, max_distance):
     assert int(got.min()) == 0 and int(got.max()) == 31
 
 
+# ------------------------------------------------------------------------------------------------ the fp64 reference encoder of tests/t5_refs.py
+def test_reference_buckets_equal_transformers():
+    import t5_refs
+    g = torch.load(os.path.join(t5_fixtures.GOLDEN_DIR, "t5_buckets.pt"), weights_only=False)
+    assert torch.equal(t5_refs.buckets(g["offsets"], 32, 128), g["32_128"].long()) and torch.equal(t5_refs.buckets(g["offsets"], 32, 64), g["32_64"].long())
+
+
+@pytest.mark.parametrize("name", ["t5_tiny", "t5_l300"])
+def test_reference_encoder_equals_transformers_fp32(name):
+    """t5_refs.encoder64 on the committed fixtures against their stored transformers-fp32 hidden states, per hidden state and per row.  Bound 1e-5: the stored
+    outputs are fp32 (transformers' fp32 run of this architecture is 2.5e-6 rel-L2 from its own fp64 run); a wrong bucket, mask or GELU variant is off by
+    percent.  Measured on last_hidden_state: t5_tiny 1.4e-6 whole, 7.6e-6 worst row; t5_l300 2.2e-6 whole, 6.0e-6 worst row (the block outputs: 0.5 - 1.1e-6 whole,
+1.8 - 2.8e-6 worst row; the embedding is exact)."""
+    import t5_refs
+    fx = t5_fixtures.load(name)
+    got = t5_refs.encoder64(fx["config"], fx["state_dict"], fx["input_ids"], fx["attention_mask"])
+    assert len(got) == len(fx["hidden_states"]) == fx["config"]["num_layers"] + 1
+    assert torch.equal(fx["hidden_states"][-1], fx["last_hidden_state"])
+    D = fx["config"]["d_model"]
+    for i, (h, want) in enumerate(zip(got, fx["hidden_states"])):
+        assert h.dtype == torch.float64 and tuple(h.shape) == tuple(want.shape)
+        whole = ((h - want.double()).norm() / want.double().norm()).item()
+        rows = t5_refs.rel_l2_rows(h.reshape(-1, D), want.reshape(-1, D)).max().item()
+        print(f"\n{name} hidden state {i}: whole {whole:.2e}, worst row {rows:.2e}", end="")
+        assert whole <= 1e-5 and rows <= 1e-5, (name, i, whole, rows)
+
+
+def test_wide_recipe_is_the_one_recorded():
+    """the seeded weights and ids of t5_refs.WIDE hash to what tests/golden/t5_wide.json holds: its yardsticks are statements about exactly these tensors"""
+    import t5_refs
+    with open(os.path.join(t5_fixtures.GOLDEN_DIR, "t5_wide.json")) as f:
+        rec = json.load(f)
+    W = t5_refs.WIDE
+    assert rec["cfg"] == t5_refs.full_config(W["cfg"]) and (rec["B"], rec["L"], rec["lens"], rec["seed"]) == (W["B"], W["L"], W["lens"], W["seed"])
+    sd = t5_refs.state_dict(W["cfg"], W["seed"])
+    ids, mask = t5_refs.inputs(W["cfg"], W["B"], W["L"], W["lens"], W["seed"])
+    assert mask.sum(1).tolist() == W["lens"] and ids.shape == (W["B"], W["L"])
+    assert all(torch.equal(v.float().to(torch.bfloat16), v) and torch.isfinite(v.float()).all() for v in sd.values())
+    assert t5_refs.checksum(sd, ids) == rec["checksum"]
+
+
 # ------------------------------------------------------------------------------------------------ argument checks
 def _attn_args(lib, **over):
     buf = (ctypes.c_char * 4096)()                         # host memory, 16-byte aligned below; a refused call reads none of it

@@ -4,7 +4,12 @@ tools/make_t5_golden.py from the class the reference calls).
 Bound: rel-L2 of last_hidden_state over ALL rows (padded ones included) <= 1.1 x the yardstick of the same fixture and operand type in
 tests/golden/t5_ref_noise.json - what transformers' own bf16 / fp16 model loses against its fp32 run on the same input; the margin is the one the project
 asserts against ref_fp16_noise.json.  A CPU emulation of this module's rounding points (operands and GEMM outputs rounded, fp32 residual and statistics, P
-rounded) lands at 0.66 - 0.87 of the yardstick; a wrong bias index or mask moves the output by tens of percent at these logit spreads."""
+rounded) lands at 0.66 - 0.87 of the yardstick; a wrong bias index or mask moves the output by tens of percent at these logit spreads.  That emulation is
+tests/t5_refs.py: encoder64(round_to=...).
+
+Both fixtures keep every GEMM below pxa_gemm's M >= 1024 and N >= 1024 threshold (the 128 x 128 kernel).  test_parity_at_production_dispatch runs a third,
+seeded one (t5_refs.WIDE; figures in tests/golden/t5_wide.json, no tensors) whose five calls per block take the instances of a production batch, against
+encoder64 in fp64."""
 import argparse
 import importlib.util
 import json
@@ -81,6 +86,66 @@ def test_parity_with_transformers_fp32(lib, name):
     print(f"\n{name} [{lib.OPERAND}]: rel-L2 {e:.3e} = {e / yard:.3f} x transformers' own {lib.OPERAND} error {yard:.3e} (bound {MARGIN}); valid rows {e_valid:.3e}, "
           f"padded rows {e_pad}", end="")
     assert e <= MARGIN * yard
+
+
+def test_parity_at_production_dispatch(lib):
+    """The encoder at a width where its five GEMM calls per block take the kernels a production batch takes (tests/test_t5_gemm_forms_gpu.py has them one by
+    one): the seeded fixture t5_wide of tests/t5_refs.py, d_model 1024, 16 heads, d_ff 1280, 2 blocks, 4 x 300 tokens with lengths 300 / 137 / 1 / 77, so
+    M = 1200 = 4 x 256 + 176 rows.  Weights and ids are regenerated from the recipe and must hash to what tests/golden/t5_wide.json records; the reference is
+    t5_refs.encoder64 in fp64 on the GPU (3.5e-7 from transformers' fp64 model, whose norm takes its variance in fp32; transformers' fp32 run is 2.0e-6 from it).
+    Asserted on last_hidden_state: rel-L2 over all rows, and over rows 1024 .. 1199 alone (the ragged last 256-row tile: padded positions of the last sample,
+    computed like every row), each <= 1.1 x transformers' own loss in the operand type on the same rows (the json's yardstick; the margin is this file's).
+    The CPU emulation of the module's rounding points (encoder64(round_to=...), in the json) lands at 0.65 (all rows) / 0.45 (tail rows) of the bf16
+    yardstick and 0.78 / 0.70 of the fp16 one.  Measured on an MI355X: bf16 build 1.277e-2 = 0.651 x the yardstick over all rows, 1.227e-2 = 0.472 x over the
+    tail rows (worst single row 3.6e-2); fp16 build 1.618e-3 = 0.769 x and 1.553e-3 = 0.667 x (worst row 4.3e-3)."""
+    import t5_refs
+    from pixart_sigma_amd import ops
+    from pixart_sigma_amd.t5 import T5Encoder
+    with open(os.path.join(t5_fixtures.GOLDEN_DIR, "t5_wide.json")) as f:
+        rec = json.load(f)
+    W = t5_refs.WIDE
+    cfg = t5_refs.full_config(W["cfg"])
+    sd = t5_refs.state_dict(W["cfg"], W["seed"])
+    ids, mask = t5_refs.inputs(W["cfg"], W["B"], W["L"], W["lens"], W["seed"])
+    assert rec["cfg"] == cfg and t5_refs.checksum(sd, ids) == rec["checksum"], "the regenerated weights / ids are not the ones t5_wide.json's figures were taken on"
+    for key in ("bf16", "f16"):                            # the condition the yardstick is usable under: the emulation itself stays inside the margin
+        for rows in ("all_rows", "tail_rows"):
+            assert rec["emulation_vs_encoder64"][key][rows] <= MARGIN * rec["yardstick"][key][rows], (key, rows)
+    # the five calls of this config name the instances of a production batch
+    M, D, inner, dff, op = W["B"] * W["L"], cfg["d_model"], cfg["num_heads"] * cfg["d_kv"], cfg["d_ff"], lib.OPERAND_DTYPE
+    assert M == 1200 and t5_refs.WIDE_TAIL == slice(1024, M)
+
+    def plan(K, N, **kw):
+        kw = {k: torch.empty(M, N, dtype=torch.float32 if k == "out_f32" else op) if k in ("aux", "out_f32") else v for k, v in kw.items()}
+        return ops.gemm_plan(torch.empty(M, K, dtype=op), torch.empty(N, K, dtype=op), ops.NT, **kw).split()
+    assert plan(D, 3 * inner)[0] == "gemm_pers_kernel<0,0,0,false>"
+    assert plan(D, dff, act=ops.ACT_GELU)[0] == "gemm_pers_kernel<0,7,0,false>"
+    assert plan(D, dff, act=ops.ACT_MUL_AUX, aux=True)[0] == "gemm_pers_kernel<0,3,0,false>"
+    for K in (inner, dff):
+        p = plan(K, D, out_f32=True, accumulate=True)
+        assert p[0] == "gemm_glds_kernel<0,256,256,2,4,0,false>" and "accumulate=2" in p and "split=1" in p, p
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                    # the fp16-build notice
+        m = T5Encoder(cfg)
+    m.load_state_dict(sd)
+    with torch.no_grad():
+        y, hidden = m.cuda()(ids, mask, output_hidden_states=True)
+    want = t5_refs.encoder64(cfg, sd, ids, mask, device="cuda")
+    assert y.dtype == torch.float32 and tuple(y.shape) == (W["B"], W["L"], D) and torch.isfinite(y).all() and len(hidden) == len(want)
+    for i, (h, g) in enumerate(zip(hidden, want)):
+        record_parity(f"t5_wide hidden state {i} (0 = embedding, last = final norm) vs encoder64", rel_l2(h, g))
+    yard = rec["yardstick"][lib.OPERAND]
+    got2, want2 = y.reshape(M, D), want[-1].reshape(M, D)
+    e_all, e_tail = rel_l2(got2, want2), rel_l2(got2[t5_refs.WIDE_TAIL], want2[t5_refs.WIDE_TAIL])
+    worst_row = t5_refs.rel_l2_rows(got2, want2).max().item()
+    record_parity(f"t5_wide last_hidden_state vs encoder64, all rows (bound = {MARGIN} x transformers' own {lib.OPERAND} error)", e_all, MARGIN * yard["all_rows"])
+    record_parity(f"t5_wide last_hidden_state vs encoder64, rows 1024 .. 1199 (bound = {MARGIN} x transformers' own {lib.OPERAND} error there)", e_tail, MARGIN * yard["tail_rows"])
+    record_parity("t5_wide error / yardstick, all rows", e_all / yard["all_rows"], MARGIN)
+    record_parity("t5_wide error / yardstick, rows 1024 .. 1199", e_tail / yard["tail_rows"], MARGIN)
+    record_parity("t5_wide last_hidden_state, worst row", worst_row)
+    print(f"\nt5_wide [{lib.OPERAND}]: all rows {e_all:.3e} = {e_all / yard['all_rows']:.3f} x yardstick {yard['all_rows']:.3e}; rows 1024 .. 1199 {e_tail:.3e} = "
+          f"{e_tail / yard['tail_rows']:.3f} x yardstick {yard['tail_rows']:.3e} (bound {MARGIN}); worst row {worst_row:.3e}", end="")
+    assert e_all <= MARGIN * yard["all_rows"] and e_tail <= MARGIN * yard["tail_rows"]
 
 
 def test_ids_at_padded_positions_change_no_valid_row(tiny):

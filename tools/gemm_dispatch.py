@@ -1,17 +1,18 @@
 """The call list that pins pxa_gemm's host-side dispatch (csrc/gemm.hip: fill_gemm, choose_gemm, launch_instance), and the script that issues it.
 
-    python tools/gemm_dispatch.py                     every call of CASES once on cuda:0, seeded inputs: per call ops.gemm_plan's line, then " | " and the
+    python tools/gemm_dispatch.py                     every call of ALL_CASES once on cuda:0, seeded inputs: per call ops.gemm_plan's line, then " | " and the
                                                       errors of what the call wrote against reference(); also meant to run under
                                                       `rocprofv3 --kernel-trace --output-format csv -- python ...`
     python tools/gemm_dispatch.py --launches x.csv    the ordered (kernel, grid, workgroup, LDS bytes) list of a kernel-trace csv, GEMM-side kernels only
     python tools/gemm_dispatch.py --check x.csv out   --launches, checked against the plan lines: per call the instance named, then the column-sum pass and
                                                       the split-K reduce where the plan says so (needs no GPU)
 
-CASES is shared with tests/test_gemm_plan.py (the expected plan lines live there) and tests/test_gemm_call_list_gpu.py (the values: prepare_outputs,
-reference and errors below, per setting in a child process each).  Each case is (name, dict): layout, M, N, K and what else the call carries.
+CASES (the denoiser's and the VAE's calls, and the refused ones), T5_CASES (the text encoder's) and ALL_CASES (both: what is run) are shared with
+tests/test_gemm_plan.py (the expected plan lines live there) and tests/test_gemm_call_list_gpu.py (the values: prepare_outputs, reference and errors below,
+per setting in a child process each).  Each case is (name, dict): layout, M, N, K and what else the call carries.
 Shapes are the smallest that reach a branch: M = 1024 rows, N = 1024 / 1152 (N % 256 == 128: the remainder column) / 1280, N = 128 / 256 / 384 for the
-convolutions, K of one or two k-units, 4096 for the cost model and explicit splits, 72 for the register-staged kernel.  SETTINGS are the environments the list
-runs under: every once-per-process knob needs a process of its own."""
+convolutions, K of one or two k-units, 4096 for the cost model and explicit splits, 72 for the register-staged kernel; the T5 encoder's forms at ragged row
+counts (1120, 1200, 900).  SETTINGS are the environments the list runs under: every once-per-process knob needs a process of its own."""
 import csv
 import os
 import re
@@ -95,6 +96,22 @@ CASES = [
     ("refuse_k_seg_32", dict(layout=NT, M=1024, N=1024, K=128, k_seg=32, refused="k_seg=32 must be a multiple of 64 dividing K=128")),
     ("refuse_stats_without_k_seg", dict(layout=NT, M=1024, N=1024, K=128, stats_plain=True, refused="gn_part needs an implicit convolution (k_seg) with a bf16 output and act 0 or 5")),
 ]
+
+
+# the T5 encoder's five calls per block (pixart_sigma_amd/t5/encoder.py), a list of their own beside the denoiser's and the VAE's: no bias anywhere, GELU with one
+# output, x aux without column sums, the fp32 residual as a single-slice accumulate target; M = B L is never a multiple of 256: 1120 = 4 x 256 + 96 (the last
+# tile's second 128-row wave row is wholly out of range), 1200 = 4 x 256 + 176 (partly in range), 900 rows: below the 1024-row threshold
+T5_CASES = [
+    ("t5_qkv_1120_rows", dict(layout=NT, M=1120, N=1536, K=128)),
+    ("t5_gelu_no_bias", dict(layout=NT, M=1120, N=1280, K=128, act=1)),
+    ("t5_mul_aux", dict(layout=NT, M=1120, N=1280, K=128, act=4)),
+    ("t5_mul_aux_1152", dict(layout=NT, M=1200, N=1152, K=128, act=4)),
+    ("t5_residual_1024", dict(layout=NT, M=1120, N=1024, K=128, f32=True, accumulate=True)),
+    ("t5_residual_k320", dict(layout=NT, M=1200, N=1280, K=320, f32=True, accumulate=True)),
+    ("t5_residual_900_rows", dict(layout=NT, M=900, N=1024, K=320, f32=True, accumulate=True)),
+]
+# what the scripts and the tests run: the launched calls, the T5 forms behind them (a case's seed is its place here), the refused calls last
+ALL_CASES = [c for c in CASES if "refused" not in c[1]] + T5_CASES + [c for c in CASES if "refused" in c[1]]
 
 
 def make_call(spec, device, seed=0, values=True):
@@ -368,7 +385,7 @@ def main():
     import torch
     from pixart_sigma_amd import ops
     from pixart_sigma_amd.lib import PixartHipError
-    for i, (name, spec) in enumerate(CASES):
+    for i, (name, spec) in enumerate(ALL_CASES):
         if "refused" in spec:
             continue
         a, b, kw = make_call(spec, "cuda:0", seed=i)

@@ -10,6 +10,7 @@ Writes
                            below the repository's 1 MiB limit; tests/t5_fixtures.py puts them together again
   t5_buckets.pt            T5Attention._relative_position_bucket for offsets -1023 .. 1023 at (32, 128) and (32, 64)
   t5_ref_noise.json        the yardstick: rel-L2 of transformers' own bf16 model, and of its fp16 model, against its fp32 output on the same input
+  t5_wide.json             a third, seeded fixture at widths >= 1024 and 1200 rows, as figures only (make_wide below; --only-wide writes it alone)
 Weights: transformers' random init, then norm weights 1 + 0.2 N(0,1), the bias embedding 2 N(0,1), q weights x 8 (unscaled logits that spread as in a trained
 T5), everything rounded to bf16."""
 import argparse
@@ -91,10 +92,55 @@ def make_fixture(name, spec, out):
     return noise
 
 
+def make_wide(out):
+    """t5_wide.json: the seeded recipe of tests/t5_refs.py (no tensor is stored: the tests regenerate weights and ids and compare the checksum) loaded into
+    transformers.T5EncoderModel; what transformers' own bf16 / fp16 model loses against its fp32 output, over all rows and over the rows of the ragged last
+    256-row tile; how far t5_refs.encoder64 is from transformers' fp64 output, and its rounding-point emulations from its fp64 output, on the same row sets."""
+    import sys
+    from transformers import T5Config, T5EncoderModel
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import t5_refs
+    W = t5_refs.WIDE
+    cfg = t5_refs.full_config(W["cfg"])
+    sd = t5_refs.state_dict(W["cfg"], W["seed"])
+    ids, mask = t5_refs.inputs(W["cfg"], W["B"], W["L"], W["lens"], W["seed"])
+    config = T5Config(dropout_rate=0.0, is_encoder_decoder=False, use_cache=False, **cfg)
+    model = T5EncoderModel(config).eval()
+    model.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
+    D, tail = cfg["d_model"], t5_refs.WIDE_TAIL
+
+    def both(got, want):
+        got, want = got.reshape(-1, D), want.reshape(-1, D)
+        return dict(all_rows=rel_l2(got, want), tail_rows=rel_l2(got[tail], want[tail]))
+    with torch.no_grad():
+        hf64 = model.double()(input_ids=ids, attention_mask=mask)["last_hidden_state"]
+        hf32 = model.float()(input_ids=ids, attention_mask=mask)["last_hidden_state"]
+        yard = {}
+        for key, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
+            low = model.to(dt)(input_ids=ids, attention_mask=mask)["last_hidden_state"].float()
+            assert torch.isfinite(low).all(), key
+            yard[key] = both(low, hf32)
+            model.float()
+    ref64 = t5_refs.encoder64(cfg, sd, ids, mask)[-1]
+    emu = {key: both(t5_refs.encoder64(cfg, sd, ids, mask, round_to=dt)[-1], ref64) for key, dt in (("bf16", torch.bfloat16), ("f16", torch.float16))}
+    rec = dict(what="the seeded fixture t5_wide of tests/t5_refs.py: rel-L2 figures of last_hidden_state, over all B L rows and over rows "
+                    f"{tail.start} .. {tail.stop - 1} (tail_rows)",
+               cfg=cfg, B=W["B"], L=W["L"], lens=W["lens"], seed=W["seed"], checksum=t5_refs.checksum(sd, ids),
+               encoder64_vs_transformers_fp64=both(ref64, hf64), transformers_fp32_vs_fp64=both(hf32, hf64),
+               yardstick=yard, emulation_vs_encoder64=emu)
+    with open(os.path.join(out, "t5_wide.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+    print("t5_wide:", json.dumps({k: rec[k] for k in ("encoder64_vs_transformers_fp64", "transformers_fp32_vs_fp64", "yardstick", "emulation_vs_encoder64")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+    ap.add_argument("--only-wide", action="store_true", help="write t5_wide.json alone and leave the stored fixtures as they are")
     a = ap.parse_args()
+    make_wide(a.out)
+    if a.only_wide:
+        return
     from transformers.models.t5.modeling_t5 import T5Attention
     noise = {name: make_fixture(name, spec, a.out) for name, spec in FIXTURES.items()}
     with open(os.path.join(a.out, "t5_ref_noise.json"), "w") as f:
