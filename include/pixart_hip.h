@@ -332,6 +332,15 @@ int pxa_vae_attn(const void* q, const void* k, const void* v, long ldq, long ldk
 /* fp32 NCHW (B, C, H, W) image / latent -> bf16 grid scaled by mul, channels C..grid.C-1 zero; and back (first C channels). */
 int pxa_vae_nchw_to_grid(const float* img, int C, float mul, const pxa_grid* y, hipStream_t stream);
 int pxa_vae_grid_to_nchw(const pxa_grid* x, int C, float* img, hipStream_t stream);
+/* (addition under ABI 11) The posterior sample at the end of AutoencoderKL.encode, in one launch (reference train_scripts/train.py:149-153: posterior =
+ * vae.encode(images).latent_dist; z = posterior.sample(); then z * scale_factor):
+ *   x0[b][c][y][x] = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps[b][c][y][x]),   c < latent_channels
+ * moments: the fp32 output of quant_conv over every pixel slot of a grid: pixel (b, y, x) is the ch_stride-vector at
+ * moments + (b*img_pitch + y*row_pitch + x + origin) * ch_stride, mean in channels [0, latent_channels), logvar in [latent_channels, 2*latent_channels).
+ * Only the H x W interior pixels and those 2*latent_channels channels are read.  eps, x0: fp32 NCHW (B, latent_channels, H, W); eps == NULL gives the mode,
+ * scale * mean.  expf, and every product and sum rounded once (no fused multiply-add).  ch_stride a multiple of 4, moments 16-byte aligned: else -1. */
+int pxa_vae_posterior(const float* moments, int B, int H, int W, int latent_channels, int ch_stride, int row_pitch, long img_pitch, long origin,
+                      const float* eps, float scale, float* x0, hipStream_t stream);
 /* Direct 3x3 stride-1 pad-1 convolution of act(norm(x)) to Cout <= 4 channels, written as an fp32 NCHW image (B, Cout, H, W): the decoder's conv_out
  * (diffusers AutoencoderKL: decoder.conv_norm_out -> SiLU -> decoder.conv_out, 128 -> 3; call site of the whole decode: reference scripts/inference.py:136).
  * One pass over x: no padded copy, no patch matrix, no crop / permute.  w_taps: [9][Cout][C] in the library's operand type (tap = ky * 3 + kx);

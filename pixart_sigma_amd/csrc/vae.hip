@@ -30,13 +30,15 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
 
 // ---- GroupNorm statistics: per (sample, group) sum and sum of squares over H*W*(C/groups) elements.
 // A thread owns one 8-channel chunk of a pixel and keeps two partial pairs (channels 0-3 / 4-7: groups are >= 4 channels wide);
-// a block folds its partials per group in LDS and adds them to the fp64 accumulators with one atomic per group.
+// a block folds its partials per group through LDS in a FIXED order (in fp64: one thread per (group, statistic) walks the 512 / groups partials that belong
+// to it) and adds the result to the fp64 accumulators with one atomic per group.  The fold used to be fp32 LDS atomics, whose order across the block's
+// wavefronts varies from launch to launch: two encodes of one picture then differed in the last bits of a mean and, after the 16-bit rounding of the
+// normalised activations, by an ulp of the operand type here and there (tests/test_vae_posterior_gpu.py needs encode to repeat).  What is left to the
+// order of arrival is the fp64 sum of the blocks' partials, whose rounding (2^-53) does not reach the fp32 mean / rstd.
 __global__ __launch_bounds__(256) void gn_stats_kernel(Grid x, int cpg, double* __restrict__ ws) {
-  __shared__ float red[2 * 256];                       // [group][sum, sumsq], groups <= 256
+  __shared__ float part[4][256];                       // [s0, q0, s1, q1][thread]
   const int CV = x.C / 8, PPB = 256 / CV, G = x.C / cpg, b = blockIdx.y;
   const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
-  for (int i = threadIdx.x; i < 2 * G; i += 256) red[i] = 0.f;
-  __syncthreads();
   float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
   for (int y = blockIdx.x; y < x.H; y += gridDim.x) {   // a block walks whole image rows: no index divisions in the loop
     const bf16_t* row = x.at(b, y, 0) + cv * 8;
@@ -47,11 +49,18 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(Grid x, int cpg, double* 
       s1 += (f[4] + f[5]) + (f[6] + f[7]); q1 += (f[4] * f[4] + f[5] * f[5]) + (f[6] * f[6] + f[7] * f[7]);
     }
   }
-  const int g0 = (cv * 8) / cpg, g1 = (cv * 8 + 4) / cpg;
-  atomicAdd(&red[2 * g0], s0); atomicAdd(&red[2 * g0 + 1], q0);
-  atomicAdd(&red[2 * g1], s1); atomicAdd(&red[2 * g1 + 1], q1);
+  part[0][threadIdx.x] = s0; part[1][threadIdx.x] = q0; part[2][threadIdx.x] = s1; part[3][threadIdx.x] = q1;
   __syncthreads();
-  for (int i = threadIdx.x; i < 2 * G; i += 256) atomicAdd(&ws[(long)b * 2 * G + i], (double)red[i]);
+  const int hpg = cpg / 4;                              // 4-channel halves of a chunk per group: half hc = 2 * cv + (0 | 1) holds channels 4 hc .. 4 hc + 3
+  for (int i = threadIdx.x; i < 2 * G; i += 256) {
+    const int g = i >> 1, stat = i & 1;
+    double acc = 0.0;
+    for (int hc = g * hpg; hc < (g + 1) * hpg; hc++) {
+      const float* p = part[2 * (hc & 1) + stat] + (hc >> 1);
+      for (int l = 0; l < PPB; l++) acc += (double)p[l * CV];
+    }
+    atomicAdd(&ws[(long)b * 2 * G + i], acc);
+  }
 }
 __global__ void gn_finalize_kernel(const double* __restrict__ ws, float* __restrict__ mean, float* __restrict__ rstd, int n_groups, double count, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -286,6 +295,43 @@ __global__ __launch_bounds__(256) void grid_to_nchw_kernel(Grid x, int C, float*
   }
 }
 
+// ---- posterior sample of the encoder: fp32 moments in quant_conv's padded-grid layout -> x0 = scale * (mean + exp(0.5 * clamp(logvar)) * eps), fp32 NCHW.
+// One thread per latent pixel, consecutive threads along w: the 2 * LC moments of a pixel are 32 contiguous bytes of a CS-float slot (one or two 16-byte loads),
+// eps and x0 are read / written channel plane by channel plane, each a coalesced run along w.  Only interior pixels and the first 2 * LC channels are read.
+// 17 MB of traffic at 16 x 128 x 128, some 12 us: a sliver of the step, so the exponential is expf and every product and sum is rounded on its own (no contraction):
+// the five roundings of the torch chain it replaces.
+constexpr int POST_MAX_BLOCKS = 2048;        // 2048 x 256 pixels per pass of the grid-stride loop
+template <int LC>
+__global__ __launch_bounds__(256) void posterior_kernel(const float* __restrict__ mom, long pixels, int H, int W, int lc, int CS, int row_pitch, long img_pitch,
+                                                        long origin, const float* __restrict__ eps, float scale, float* __restrict__ x0) {
+  const int n = LC ? LC : lc;
+  const long HW = (long)H * W;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long)gridDim.x * 256) {
+    const long b = p / HW, r = p - b * HW;
+    const int yy = (int)(r / W), xx = (int)(r - (long)yy * W);
+    const float* src = mom + (b * img_pitch + (long)yy * row_pitch + xx + origin) * CS;
+    float m[LC ? 2 * LC : 1];
+    if constexpr (LC == 4) {
+      const float4 a = *reinterpret_cast<const float4*>(src), c = *reinterpret_cast<const float4*>(src + 4);
+      m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = c.x; m[5] = c.y; m[6] = c.z; m[7] = c.w;
+    } else if constexpr (LC == 2) {
+      const float4 a = *reinterpret_cast<const float4*>(src);
+      m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
+    }
+    const long o = b * n * HW + r;
+#pragma unroll
+    for (int c = 0; c < n; c++) {
+      const float mean = LC ? m[LC ? c : 0] : src[c];
+      float v = mean;
+      if (eps) {
+        const float lv = fminf(fmaxf(LC ? m[LC ? LC + c : 0] : src[n + c], -30.f), 20.f);
+        v = __fadd_rn(mean, __fmul_rn(expf(0.5f * lv), eps[o + c * HW]));
+      }
+      x0[o + c * HW] = __fmul_rn(scale, v);
+    }
+  }
+}
+
 static int check_grid(const pxa_grid* g, const char* what) {
   PXA_CHECK(g && g->ptr, "%s: null grid", what);
   PXA_CHECK(g->B > 0 && g->H > 0 && g->W > 0 && g->C > 0 && g->C % 8 == 0, "%s: bad grid %d x %d x %d x %d (C must be a multiple of 8)", what, g->B, g->H, g->W, g->C);
@@ -395,6 +441,27 @@ extern "C" int pxa_vae_grid_to_nchw(const pxa_grid* x, int C, float* img, hipStr
   PXA_CHECK(img && C > 0 && C <= x->C, "pxa_vae_grid_to_nchw: bad channel count %d (grid has %d)", C, x->C);
   PXA_CHECK(x->H <= 65535 && x->B <= 65535, "pxa_vae_grid_to_nchw: grid too large");
   hipLaunchKernelGGL(grid_to_nchw_kernel, dim3((x->W + 255) / 256, x->H, x->B), dim3(256), 0, stream, to_grid(x), C, img);
+  PXA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pxa_vae_posterior(const float* moments, int B, int H, int W, int latent_channels, int ch_stride, int row_pitch, long img_pitch, long origin,
+                                 const float* eps, float scale, float* x0, hipStream_t stream) {
+  PXA_CHECK(moments && x0, "pxa_vae_posterior: null moments or output");
+  PXA_CHECK(B > 0 && H > 0 && W > 0 && latent_channels > 0, "pxa_vae_posterior: bad shape %d x %d x %d x %d", B, latent_channels, H, W);
+  PXA_CHECK(ch_stride >= 2 * latent_channels && ch_stride % 4 == 0 && ((uintptr_t)moments & 15) == 0,
+            "pxa_vae_posterior: channel stride %d must be a multiple of 4 and >= 2 * %d, moments 16-byte aligned", ch_stride, latent_channels);
+  PXA_CHECK(row_pitch >= W && img_pitch >= (long)(H - 1) * row_pitch + W && origin >= 0, "pxa_vae_posterior: bad pitches");
+  const long pixels = (long)B * H * W;
+  const int blocks = (pixels + 255) / 256 < POST_MAX_BLOCKS ? (int)((pixels + 255) / 256) : POST_MAX_BLOCKS;
+#define PXA_POST(LC) hipLaunchKernelGGL(posterior_kernel<LC>, dim3(blocks), dim3(256), 0, stream, moments, pixels, H, W, latent_channels, ch_stride, row_pitch, \
+                                        img_pitch, origin, eps, scale, x0)
+  switch (latent_channels) {
+    case 4: PXA_POST(4); break;
+    case 2: PXA_POST(2); break;
+    default: PXA_POST(0); break;
+  }
+#undef PXA_POST
   PXA_LAUNCH_CHECK();
   return 0;
 }

