@@ -382,6 +382,37 @@ typedef struct {
 } pxa_t5_attn_args;
 int pxa_t5_attn(const pxa_t5_attn_args* args, hipStream_t stream);
 
+/* FP8 weight storage for the T5 encoder (csrc/gemm_w8.hip).  A matrix W [N][K] is held as q [N][K], one OCP e4m3fn byte per element with row pitch ldq bytes,
+ * and scale [N] fp32: W ~ scale[n] * q[n][k].  K a multiple of 16; ldq >= K and a multiple of 16; 16-bit and fp32 pitches (elements) multiples of 8; q, the
+ * 16-bit / fp32 matrices and scale 16-byte aligned.
+ * pxa_fp8_quant_rows: src [N][K] with row pitch ld, in the operand type or (src_is_f32) fp32 ->  scale[n] = 2^ceil(log2(max_k |src[n][k]| / 448)), 1 for an
+ *   all-zero row and never below 2^-126;  q = e4m3fn(float(src) / scale[n]), the quotient exact, clamped to +-448, rounded to nearest even: the NaN codes
+ *   0x7F / 0xFF are never written.  One workgroup per row; nothing behind column K of a row is read or written.
+ * pxa_fp8_dequant_rows: dst[n][k] = scale[n] * q[n][k] (an fp32 product) rounded once to the operand type, row pitch ld.  Exact for a power-of-two scale
+ *   (in fp16: where the product is a normal number); any other scale costs that one rounding. */
+int pxa_fp8_quant_rows(const void* src, int src_is_f32, long ld, int N, int K, void* q, long ldq, float* scale, hipStream_t stream);
+int pxa_fp8_dequant_rows(const void* q, long ldq, const float* scale, int N, int K, void* dst, long ld, hipStream_t stream);
+/* pxa_gemm_w8: C[m][n] = scale[n] * sum_k A[m][k] q[n][k] (NT), A [M][K] of the operand type with row pitch lda, for the row counts of one prompt or a few:
+ * 1 <= M <= pxa_gemm_w8_max_m(), N a multiple of 8, K a multiple of 16.  The FP8 bytes are widened (exactly) to the operand type in registers and multiplied on the
+ * 16-bit MFMA into fp32; the activations are not quantised; the scale multiplies the fp32 sum.  Exactly one of out16 / out_f32:
+ *   out16 (operand type, pitch ld_out):  act 0 = the value; act 1 = GELU(tanh) of it; act 4 = the value times aux[m][n] (operand type, pitch ldaux); rounded once;
+ *   out_f32 (pitch ld_f32), act 0:       out_f32[m][n] += value, a plain read-modify-write (the fp32 residual stream).
+ * act uses pxa_gemm's codes.  No K split, no atomics, no workspace: two calls on the same inputs give the same bits.  Every limit is checked before any HIP
+ * call (-1 and pxa_last_error).  pxa_gemm_w8_plan: the same checks with the same return codes and, for a call that would launch, one line of text
+ * "<kernel instance> split=1 bm=.. bn=.. bk=.. m_tiles=.. n_tiles=.. grid=.." (no GPU needed; pointers are only tested for NULL and alignment). */
+typedef struct {
+  const void* A; long lda;
+  const void* q; long ldq;
+  const float* scale;
+  int M, N, K, act;
+  const void* aux; long ldaux;
+  void* out16; long ld_out;
+  float* out_f32; long ld_f32;
+} pxa_gemm_w8_args;
+int pxa_gemm_w8(const pxa_gemm_w8_args* args, hipStream_t stream);
+int pxa_gemm_w8_plan(const pxa_gemm_w8_args* args, char* out, int out_len);
+int pxa_gemm_w8_max_m(void);
+
 /* ---------------------------------------------------------------------------------------------- LoRA adapters
  * y = x (W + s B A)^T + b with A [r][K], B [N][r] stored transposed as Bt [r][N]: what peft's LoraLayer computes for the reference's fine-tuning scripts
  * (train_scripts/train_pixart_lora_hf.py:505-524).  The adapter is folded into the 16-bit operand copy of W, so every forward / dX GEMM runs unchanged;

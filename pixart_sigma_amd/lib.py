@@ -77,6 +77,13 @@ class T5AttnArgs(C.Structure):
                 ("B", c_int), ("H", c_int), ("L", c_int), ("head_dim", c_int)]
 
 
+class GemmW8Args(C.Structure):
+    """pxa_gemm_w8_args (include/pixart_hip.h, FP8 weight storage of the T5 encoder)."""
+    _fields_ = [("A", c_void_p), ("lda", c_long), ("q", c_void_p), ("ldq", c_long), ("scale", c_void_p),
+                ("M", c_int), ("N", c_int), ("K", c_int), ("act", c_int),
+                ("aux", c_void_p), ("ldaux", c_long), ("out16", c_void_p), ("ld_out", c_long), ("out_f32", c_void_p), ("ld_f32", c_long)]
+
+
 # name -> argtypes (all return int); must list every symbol include/pixart_hip.h declares
 _P, _I, _L, _F = c_void_p, c_int, c_long, c_float
 _G = C.POINTER(GridArg)
@@ -124,13 +131,17 @@ SIGNATURES = {
     "pxa_t5_embed": [_P, _P, _P, _I, _I, _I, _P],
     "pxa_t5_rmsnorm": [_P, _P, _P, _P, _I, _I, _F, _P],
     "pxa_t5_attn": [C.POINTER(T5AttnArgs), _P],
+    "pxa_fp8_quant_rows": [_P, _I, _L, _I, _I, _P, _L, _P, _P],
+    "pxa_fp8_dequant_rows": [_P, _L, _P, _I, _I, _P, _L, _P],
+    "pxa_gemm_w8": [C.POINTER(GemmW8Args), _P],
     "pxa_lora_merge": [_P, _L, _I, _I, _I, _P, _P, _L, _I, _F, _P, _L, _P, _L, _I, _I, _F, _P, _P],
     "pxa_lora_bwd": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "pxa_image_resample": [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P],
     "pxa_image_to_u8": [_P, _I, _L, _I, _I, _P, _P],
 }
 OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan", "pxa_attn_plan",
-                 "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes", "pxa_vae_posterior"]
+                 "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes", "pxa_vae_posterior",
+                 "pxa_gemm_w8_plan", "pxa_gemm_w8_max_m"]
 
 _lib = None
 
@@ -161,6 +172,8 @@ def load():
     lib.pxa_attn_plan.argtypes, lib.pxa_attn_plan.restype = [C.POINTER(AttnArgs), c_int, C.c_char_p, c_int], c_int
     lib.pxa_lora_bwd_ws_bytes.argtypes, lib.pxa_lora_bwd_ws_bytes.restype = [c_long, c_int, c_int, c_int], c_long
     lib.pxa_image_resample_ws_bytes.argtypes, lib.pxa_image_resample_ws_bytes.restype = [c_int, c_int], c_long
+    lib.pxa_gemm_w8_plan.argtypes, lib.pxa_gemm_w8_plan.restype = [C.POINTER(GemmW8Args), C.c_char_p, c_int], c_int
+    lib.pxa_gemm_w8_max_m.argtypes, lib.pxa_gemm_w8_max_m.restype = [], c_int
     lib.pxa_mfma_rate_probe_bytes.argtypes, lib.pxa_mfma_rate_probe_bytes.restype = [], c_long
     # bound here and not in SIGNATURES: tests/test_vae_kernel_forms_gpu.py holds the pxa_vae_* entries of SIGNATURES against its own list of refused calls
     lib.pxa_vae_posterior.argtypes, lib.pxa_vae_posterior.restype = [_P, _I, _I, _I, _I, _I, _I, _L, _L, _P, _F, _P, _P], c_int

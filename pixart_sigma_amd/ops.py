@@ -696,6 +696,102 @@ def t5_attention(q, k, v, bias, kv_len, B, H, L, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ FP8 (e4m3fn) weights of the T5 encoder
+FP8 = torch.float8_e4m3fn
+
+
+def _chk_fp8(q, scale, cuda=True):
+    assert (q.is_cuda or not cuda) and q.dtype == FP8 and q.dim() == 2 and q.stride(1) == 1, "q: need a 2-D contiguous-last-dim float8_e4m3fn CUDA tensor"
+    _chk(scale, F32, "scale", cuda=cuda)
+    assert scale.dim() == 1 and scale.numel() == q.shape[0], f"scale: need ({q.shape[0]},) fp32, got {tuple(scale.shape)}"
+
+
+def fp8_quant_rows(w, q=None, scale=None):
+    """The project's FP8 quantiser (pxa_fp8_quant_rows): w (N, K) of the operand type or fp32 -> (q (N, K) float8_e4m3fn, scale (N,) fp32) with
+    scale[n] = 2^ceil(log2(max_k |w[n][k]| / 448)) (1 for an all-zero row) and q = e4m3fn(w / scale), round to nearest even, saturating at +-448."""
+    assert w.is_cuda and w.dim() == 2 and w.stride(1) == 1 and w.dtype in (BF16, F32), f"fp8_quant_rows: need a 2-D CUDA tensor of {BF16} or fp32, got {w.dtype}"
+    N, K = w.shape
+    if q is None:
+        q = torch.empty(N, K, dtype=FP8, device=w.device)
+    if scale is None:
+        scale = torch.empty(N, dtype=F32, device=w.device)
+    _chk_fp8(q, scale)
+    assert tuple(q.shape) == (N, K)
+    call("pxa_fp8_quant_rows", ptr(w), int(w.dtype == F32), w.stride(0), N, K, ptr(q), q.stride(0), ptr(scale))
+    return q, scale
+
+
+def fp8_dequant_rows(q, scale, out=None):
+    """out[n][k] = scale[n] * q[n][k] rounded once to the operand type (pxa_fp8_dequant_rows): exact for a power-of-two scale.  out may be a (N, K) view of a
+    larger buffer (the encoder's one scratch matrix)."""
+    _chk_fp8(q, scale)
+    N, K = q.shape
+    if out is None:
+        out = torch.empty(N, K, dtype=BF16, device=q.device)
+    _chk(out, BF16, "out")
+    assert tuple(out.shape) == (N, K)
+    call("pxa_fp8_dequant_rows", ptr(q), q.stride(0), ptr(scale), N, K, ptr(out), out.stride(0))
+    return out
+
+
+def gemm_w8_max_m():
+    return lib.load().pxa_gemm_w8_max_m()
+
+
+_W8_SOMEWHERE = (C.c_char * 32)()
+
+
+def _gemm_w8_args(plan, a, q, scale, act, aux, out, out_f32):
+    def chk(t, dtype, name):
+        if not isinstance(t, _Unallocated):
+            _chk(t, dtype, name, cuda=not plan)
+
+    def ptr(t):                    # the plan entry tests alignment: a 16-byte aligned address stands for a buffer gemm_w8 would allocate
+        return C.c_void_p((C.addressof(_W8_SOMEWHERE) + 15) & ~15) if isinstance(t, _Unallocated) else lib.ptr(t, cuda=not plan)
+    chk(a, BF16, "A")
+    _chk_fp8(q, scale, cuda=not plan)
+    M, K = a.shape
+    N, K2 = q.shape
+    assert K == K2, f"gemm_w8: K mismatch {K} vs {K2}"
+    g = lib.GemmW8Args()
+    g.A, g.lda, g.q, g.ldq, g.scale = ptr(a), a.stride(0), ptr(q), q.stride(0), ptr(scale)
+    g.M, g.N, g.K, g.act = M, N, K, act
+    if act == ACT_MUL_AUX:
+        chk(aux, BF16, "aux")
+        assert tuple(aux.shape) == (M, N)
+        g.aux, g.ldaux = ptr(aux), aux.stride(0)
+    if out_f32 is not None:
+        assert out is None, "gemm_w8: out and out_f32 exclude each other"
+        chk(out_f32, F32, "out_f32")
+        assert tuple(out_f32.shape) == (M, N)
+        g.out_f32, g.ld_f32 = ptr(out_f32), out_f32.stride(0)
+        return g, out_f32
+    if out is None:
+        out = _Unallocated(M, N, BF16) if plan else torch.empty((M, N), dtype=BF16, device=a.device)
+    chk(out, BF16, "out")
+    assert tuple(out.shape) == (M, N)
+    g.out16, g.ld_out = ptr(out), out.stride(0)
+    return g, out
+
+
+def gemm_w8(a, q, scale, act=ACT_NONE, aux=None, out=None, out_f32=None):
+    """scale[n] * sum_k a[m][k] q[n][k] with FP8 weights streamed against 16-bit activations (pxa_gemm_w8).  a (M, K) operand type, q (N, K) float8_e4m3fn,
+    scale (N,) fp32.  act: ACT_NONE, ACT_GELU or ACT_MUL_AUX (with aux (M, N)) into a 16-bit `out` (allocated if not given), or out_f32 (M, N) fp32 given:
+    out_f32 += the product.  Returns the tensor written."""
+    g, res = _gemm_w8_args(False, a, q, scale, act, aux, out, out_f32)
+    call("pxa_gemm_w8", C.byref(g))
+    return res
+
+
+def gemm_w8_plan(a, q, scale, act=ACT_NONE, aux=None, out=None, out_f32=None):
+    """pxa_gemm_w8_plan's line for the call gemm_w8 would make (kernel instance, split, tiles); raises what gemm_w8 would raise for a call the library
+    refuses.  Needs no GPU: the tensors may live on any device."""
+    g, _ = _gemm_w8_args(True, a, q, scale, act, aux, out, out_f32)
+    buf = C.create_string_buffer(256)
+    lib.check(lib.load().pxa_gemm_w8_plan(C.byref(g), buf, len(buf)), "pxa_gemm_w8_plan")
+    return buf.value.decode()
+
+
 def vae_nchw_to_grid(img, y, mul=1.0):
     _chk(img, F32, "image")
     assert img.is_contiguous() and img.shape[0] == y.B and img.shape[2] == y.H and img.shape[3] == y.W

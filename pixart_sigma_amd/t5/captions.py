@@ -95,7 +95,7 @@ class _Worker:
     """The child process of the f16 build's CaptionEncoder and the parent's end of its protocol.  Requests are lines on the child's stdin
     ("<TAG> <slot> <B>"), answers lines on its stdout ("<TAG> ok <slot>"); everything else the child prints is ignored."""
 
-    def __init__(self, t5_path, L, device_index, max_batch, timeout, start_timeout):
+    def __init__(self, t5_path, L, device_index, max_batch, timeout, start_timeout, weight_dtype=None):
         from multiprocessing import shared_memory
         with open(os.path.join(t5_path, "config.json")) as f:
             self.d_model = int(json.load(f).get("d_model", 4096))
@@ -108,7 +108,7 @@ class _Worker:
         root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "") if env.get("PYTHONPATH") else root
         self.proc = subprocess.Popen([sys.executable, "-m", "pixart_sigma_amd.t5.captions", "--worker", "--t5-path", t5_path, "--shm", self.shm.name,
-                                      "--length", str(L), "--max-batch", str(max_batch), "--device", str(device_index)],
+                                      "--length", str(L), "--max-batch", str(max_batch), "--device", str(device_index)] + (["--weight-dtype", weight_dtype] if weight_dtype else []),
                                      stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=self.errfile, env=env, cwd=root)
         self._finalizer = weakref.finalize(self, _stop, self.proc, self.shm, self.errfile)
         self._buf = b""
@@ -221,9 +221,13 @@ class CaptionEncoder:
     t5_path: a transformers T5 directory (config.json + weights; T5Encoder.from_pretrained).  tokenizer: any callable with the transformers tokenizer call
     signature returning 'input_ids' and 'attention_mask'; None loads AutoTokenizer from t5_path.  max_batch sizes the worker's shared block
     (2 * max_batch * L * d_model * 2 bytes of features: 79 MB at 16 captions of 300 tokens).  timeout / start_timeout: the worker's time limits in seconds.
-    worker: None takes the worker exactly when the process runs the f16 build; True takes it under the bf16 build as well."""
+    worker: None takes the worker exactly when the process runs the f16 build; True takes it under the bf16 build as well.
+    weight_dtype: None (as stored) or "fp8_e4m3" (T5Encoder.from_pretrained); handed to the worker on its command line."""
 
-    def __init__(self, t5_path, tokenizer=None, model_max_length=300, device="cuda", max_batch=16, timeout=120.0, start_timeout=900.0, worker=None):
+    def __init__(self, t5_path, tokenizer=None, model_max_length=300, device="cuda", max_batch=16, timeout=120.0, start_timeout=900.0, worker=None,
+                 weight_dtype=None):
+        from .encoder import check_weight_dtype
+        self.weight_dtype = check_weight_dtype(weight_dtype)
         if tokenizer is None:
             from transformers import AutoTokenizer
             tokenizer = AutoTokenizer.from_pretrained(t5_path)
@@ -238,9 +242,10 @@ class CaptionEncoder:
         self._tickets = []
         if self.in_process:
             from .encoder import T5Encoder
-            self.encoder = T5Encoder.from_pretrained(t5_path, device=self.device)
+            self.encoder = T5Encoder.from_pretrained(t5_path, device=self.device, weight_dtype=weight_dtype)
         else:
-            self.worker = _Worker(t5_path, self.model_max_length, self.device.index or 0, int(max_batch), float(timeout), float(start_timeout))
+            self.worker = _Worker(t5_path, self.model_max_length, self.device.index or 0, int(max_batch), float(timeout), float(start_timeout),
+                                  weight_dtype=weight_dtype)
 
     def submit(self, texts):
         """Tokenise and start encoding; returns the host mask.  At most two submits may be outstanding; collect() returns them in order."""
@@ -288,6 +293,7 @@ def _worker_main(argv):
     ap.add_argument("--length", type=int, required=True)
     ap.add_argument("--max-batch", type=int, required=True)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--weight-dtype", default=None)
     a = ap.parse_args(argv)
     assert lib.OPERAND == "bf16", "the caption worker must run under the bf16-operand build"
     signal.signal(signal.SIGTERM, lambda *_: sys.exit(143))          # leave through the interpreter's own shutdown, not in the middle of a call
@@ -296,7 +302,7 @@ def _worker_main(argv):
     from .encoder import T5Encoder
     torch.cuda.set_device(a.device)
     dev = torch.device("cuda", a.device)
-    enc = T5Encoder.from_pretrained(a.t5_path, device=dev)
+    enc = T5Encoder.from_pretrained(a.t5_path, device=dev, weight_dtype=a.weight_dtype)
     L, D = a.length, enc.config.d_model
     offsets, size = _shm_layout(a.max_batch, L, D)
     shm = shared_memory.SharedMemory(name=a.shm)

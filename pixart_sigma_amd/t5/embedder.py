@@ -15,10 +15,11 @@ class T5Embedder:
         self.encoder, self.tokenizer, self.model_max_length = encoder, tokenizer, int(model_max_length)
 
     @classmethod
-    def from_pretrained(cls, path, device="cuda", model_max_length=120, tokenizer_path=None):
-        """T5Encoder.from_pretrained(path) plus the tokenizer of the same directory; transformers is imported here, and only for the tokenizer."""
+    def from_pretrained(cls, path, device="cuda", model_max_length=120, tokenizer_path=None, weight_dtype=None):
+        """T5Encoder.from_pretrained(path) plus the tokenizer of the same directory; transformers is imported here, and only for the tokenizer.
+        weight_dtype: None (as stored: an FP8 directory gives an FP8 encoder) or "fp8_e4m3" (quantise a 16-bit checkpoint while loading)."""
         from transformers import AutoTokenizer
-        return cls(T5Encoder.from_pretrained(path, device=device), AutoTokenizer.from_pretrained(tokenizer_path or path), model_max_length)
+        return cls(T5Encoder.from_pretrained(path, device=device, weight_dtype=weight_dtype), AutoTokenizer.from_pretrained(tokenizer_path or path), model_max_length)
 
     def get_text_embeddings(self, texts):
         tok = self.tokenizer(texts, max_length=self.model_max_length, padding="max_length", truncation=True, return_attention_mask=True,

@@ -52,6 +52,7 @@ def get_args():
     p.add_argument("--kv_compress_layers", default="14-27")
     p.add_argument("--synthetic", action="store_true", help="random caption features (plumbing check without T5 weights)")
     p.add_argument("--t5_path", default=None, type=str, help="transformers T5 directory (weights + tokenizer): encode the prompts with the in-repo T5 encoder first")
+    p.add_argument("--t5_weight_dtype", default=None, choices=["fp8_e4m3"], help="with --t5_path: hold the T5 encoder's matrices as FP8 e4m3 (default: as stored)")
     p.add_argument("--t5_timeout", default=1800, type=int, help="seconds the T5 child process may take")
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
     p.add_argument("--lora_path", default=None, type=str, help="peft-format adapter directory (adapter_config.json + adapter_model.safetensors) for the transformer blocks")
@@ -78,7 +79,8 @@ def load_captions(args, n, L, dev, first=0):
 def t5_child_command(args, prompts_file, out_dir, L):
     """The command line of the T5 child process of --t5_path (tools/extract_t5_features.py)."""
     tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "extract_t5_features.py")
-    return [sys.executable, tool, "--t5_path", args.t5_path, "--prompts", prompts_file, "--out", out_dir, "--max_length", str(L)]
+    cmd = [sys.executable, tool, "--t5_path", args.t5_path, "--prompts", prompts_file, "--out", out_dir, "--max_length", str(L)]
+    return cmd + (["--weight_dtype", args.t5_weight_dtype] if getattr(args, "t5_weight_dtype", None) else [])
 
 
 def encode_prompts(args, prompts, L):

@@ -3,11 +3,12 @@
 `caption_feature` (1, L, d_model) fp32 and `attention_mask` (1, L) int64, plus null.npz for the empty prompt (the reference's tools/extract_features.py and
 the null caption of its scripts/inference.py).
 
-    python tools/extract_t5_features.py --t5_path DIR --out DIR (--prompts FILE | --ids FILE) [--max_length 300]
+    python tools/extract_t5_features.py --t5_path DIR --out DIR (--prompts FILE | --ids FILE) [--max_length 300] [--weight_dtype fp8_e4m3]
 
 --prompts: one caption per line, tokenised with the tokenizer in --t5_path (needs `transformers` and the directory's spiece.model).
 --ids:     a torch file with `input_ids` and `attention_mask` (N, L), optionally `null_input_ids` / `null_attention_mask` (1, L) - no tokenizer needed.
            Without the null entries the empty prompt is T5's: the end-of-sequence token (id 1) alone, padded with id 0.
+--weight_dtype fp8_e4m3: quantise a 16-bit checkpoint to FP8 weights while loading (an FP8 directory, e.g. from tools/quantize_t5.py, is FP8 without it).
 The process runs under the bf16 operand build whatever the caller's environment says: the reference runs T5 in bf16 and real XXL weights overflow fp16."""
 import argparse
 import os
@@ -64,12 +65,13 @@ def main():
     ap.add_argument("--tokenizer_path", default=None)
     ap.add_argument("--max_length", default=300, type=int)
     ap.add_argument("--batch", default=8, type=int)
+    ap.add_argument("--weight_dtype", default=None, choices=["fp8_e4m3"], help="hold the encoder's matrices as FP8 e4m3 (default: as stored in --t5_path)")
     args = ap.parse_args()
     if bool(args.prompts) == bool(args.ids):
         ap.error("give exactly one of --prompts and --ids")
     from pixart_sigma_amd.t5 import T5Encoder
     ids, mask, null_ids, null_mask = tokenise(args)
-    enc = T5Encoder.from_pretrained(args.t5_path, device="cuda")
+    enc = T5Encoder.from_pretrained(args.t5_path, device="cuda", weight_dtype=args.weight_dtype)
     feats = torch.cat([enc(ids[i:i + args.batch], mask[i:i + args.batch]).cpu() for i in range(0, ids.shape[0], args.batch)])
     names = write_features(args.out, feats, mask, enc(null_ids, null_mask).cpu(), null_mask)
     print(f"wrote {len(names)} files to {args.out}: caption_feature {tuple(feats.shape[1:])} per prompt")

@@ -75,6 +75,7 @@ DEFAULTS = dict(model="PixArtMS_XL_2", image_size=1024, train_batch_size=16, num
                 log_interval=20, save_model_steps=1000, seed=43, data_root=None, load_vae_feat=True,
                 # pictures instead of feature files (reference train.py:144-168): see load_config for the `data` dict of the reference's configs
                 load_t5_feat=True, sample_posterior=True, t5_path="output/pretrained_models/pixart_sigma_sdxlvae_T5_diffusers/text_encoder", num_workers=4,
+                t5_weight_dtype=None,                  # "fp8_e4m3": the T5 encoder of text captions holds its matrices as FP8 (quantised while loading)
                 real_prompt_ratio=1.0, image_list_json="data_info.json", data_type=None, data_subdir=None,
                 vae_pretrained="output/pretrained_models/pixart_sigma_sdxlvae_T5_diffusers/vae",
                 # schedule / scaling keys of the reference configs (configs/PixArt_xl2_internal.py:34-57)
@@ -162,6 +163,8 @@ def load_config(path, debug=False):
     if cfg["load_t5_feat"] and r != 1.0:             # FeatureDatasetMS and the caption-file mode of the picture datasets always take the real prompt
         raise SystemExit(f"{path}: these settings change what is trained and only one value is implemented here: real_prompt_ratio={r!r} (implemented: 1.0) "
                          "with caption feature files (load_t5_feat=True); any value in [0, 1] needs text captions (load_t5_feat=False)")
+    if cfg["t5_weight_dtype"] not in (None, "fp8_e4m3"):
+        raise SystemExit(f"{path}: t5_weight_dtype={cfg['t5_weight_dtype']!r} is not implemented (None or 'fp8_e4m3')")
     if cfg["load_vae_feat"] and not cfg["load_t5_feat"]:
         raise SystemExit(f"{path}: load_vae_feat=True with load_t5_feat=False (latent files with text captions) is not implemented")
     if debug:
@@ -231,7 +234,7 @@ def picture_batches(cfg, B, L, dev, rank, world, vae):
             raise SystemExit(f"t5_path={cfg['t5_path']!r} is not a directory: text captions (load_t5_feat=False) need the T5 encoder's weights")
         from transformers import AutoTokenizer
         tokenizer = AutoTokenizer.from_pretrained(tok_dir if os.path.isdir(tok_dir) else cfg["t5_path"])
-        captions = CaptionEncoder(cfg["t5_path"], tokenizer, model_max_length=L, device=dev, max_batch=B)
+        captions = CaptionEncoder(cfg["t5_path"], tokenizer, model_max_length=L, device=dev, max_batch=B, weight_dtype=cfg["t5_weight_dtype"])
     it = PictureBatches(ds, B, ratios, vae, captions, cfg["seed"], rank, world, device=dev, num_workers=cfg["num_workers"], valid_num=cfg["valid_num"],
                         scale=cfg["scale_factor"], sample_posterior=cfg["sample_posterior"])
     return iter(it), captions
