@@ -19,7 +19,6 @@ of section 5 of the survey.
 import argparse
 import glob
 import os
-import runpy
 import sys
 import time
 
@@ -29,41 +28,11 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-def _run_config(path, _seen=()):
-    """A reference config file as a dict, with its `_base_` parents (mmcv convention, paths relative to the file: 13 of the reference configs inherit
-    ../PixArt_xl2_internal.py) resolved first and overridden by the child."""
-    path = os.path.abspath(path)
-    if path in _seen:
-        raise SystemExit(f"{path}: circular _base_")
-    ns = runpy.run_path(path)
-    out = {}
-    bases = ns.get("_base_", [])
-    for b in ([bases] if isinstance(bases, str) else bases):
-        out.update(_run_config(os.path.join(os.path.dirname(path), b), _seen + (path,)))
-    out.update({k: v for k, v in ns.items() if not k.startswith("_") and not callable(v) and not isinstance(v, type(os))})
-    return out
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
+from config_file import early_mixed_precision, run_config  # noqa: E402
 
-
-def _early_dtype():
-    """The MFMA operand type is a per-process choice (one library per type) and must be known before pixart_sigma_amd is imported:
-    `mixed_precision = 'fp16'` in the config (every reference config: configs/PixArt_xl2_internal.py:57) selects the fp16-operand build +
-    dynamic loss scaling, 'bf16' the bf16 build, 'no' / 'fp32' are refused (there is no fp32-operand MFMA path)."""
-    cfgs = [a for a in sys.argv[1:] if a.endswith(".py") and os.path.exists(a)]
-    mp = "bf16"
-    if cfgs:
-        mp = _run_config(cfgs[0]).get("mixed_precision", "bf16")
-    early = argparse.ArgumentParser(add_help=False)          # both `--mixed-precision fp16` and `--mixed-precision=fp16`
-    early.add_argument("--mixed-precision", default=None)
-    mp = early.parse_known_args(sys.argv[1:])[0].mixed_precision or mp
-    if mp not in ("fp16", "bf16"):
-        raise SystemExit(f"mixed_precision={mp!r}: this path computes with bf16 or fp16 MFMA operands only")
-    if mp == "fp16":
-        os.environ["PXA_OPERAND_DTYPE"] = "f16"
-    return mp
-
-
-MIXED_PRECISION = _early_dtype() if __name__ == "__main__" else "bf16"
+MIXED_PRECISION = early_mixed_precision(sys.argv[1:]) if __name__ == "__main__" else "bf16"   # before the library is imported: see config_file.py
 from pixart_sigma_amd import IDDPM, build_model  # noqa: E402
 from pixart_sigma_amd.dp import FusedAdamW, FusedCAME, LossScaler  # noqa: E402
 from pixart_sigma_amd.lr_schedule import LRSchedule, auto_scale_lr  # noqa: E402
@@ -83,10 +52,9 @@ DEFAULTS = dict(model="PixArtMS_XL_2", image_size=1024, train_batch_size=16, num
                 mixed_precision="bf16", aspect_ratio_type=None, valid_num=0, num_steps_per_epoch=None)
 # keys of reference configs that name subsystems outside this path and cannot change what is trained: accepted and ignored.
 # Anything else that is not in DEFAULTS raises: a recognised-but-unsupported option must not silently change what is trained.
-IGNORED_KEYS = {"work_dir", "log_interval", "eval_sampling_steps", "visualize", "resume_from", "load_from",
+IGNORED_KEYS = {"work_dir", "eval_sampling_steps", "visualize", "resume_from", "load_from",
                 "validation_prompts", "save_model_epochs", "window_block_indexes", "window_size", "use_rel_pos", "lewei_scale", "pe_interpolation", "roots",
-                "vae_pretrained", "tracker_project_name", "name", "num_ddim_timesteps", "w_max", "w_min", "cfg_scale", "image_size", "data_root",
-                "aspect_ratio_type", "eval_metric", "model_max_length", "max_length",
+                "tracker_project_name", "name", "num_ddim_timesteps", "w_max", "w_min", "cfg_scale", "eval_metric", "max_length",
                 # the rest of configs/PixArt_xl2_internal.py, which every PixArt-Sigma config inherits: validation, logging and storage settings, and two
                 # names (lora_rank, num_group_tokens) the reference's train.py never reads
                 "eval_batch_size", "deterministic_validation", "save_image_epochs", "tensorboard_mox_interval", "s3_work_dir", "lora_rank", "num_group_tokens"}
@@ -114,12 +82,15 @@ def parse_args():
 
 
 def batches(cfg, B, lat, L, dev, rank, world, synthetic):
+    """Flat feature files or synthetic data; yields (z, y, mask, data_info), z unscaled (noise images of 8 * lat pixels with load_vae_feat = False)."""
+    # micro-conditioning inputs (reference train.py:156): these sources have one square size, that of the picture
+    info = {"img_hw": torch.tensor([[lat * 8.0, lat * 8.0]] * B), "aspect_ratio": torch.tensor([[1.0]] * B)}
     if synthetic or not cfg["data_root"]:
         g = torch.Generator().manual_seed(cfg["seed"] + rank)
         while not cfg["load_vae_feat"]:                                            # images in, latents from the VAE inside the step
-            yield torch.randn(B, 3, lat * 8, lat * 8, generator=g).clamp(-1, 1).to(dev), torch.randn(B, 1, L, 4096, generator=g).to(dev), torch.ones(B, L, dtype=torch.int64)
+            yield torch.randn(B, 3, lat * 8, lat * 8, generator=g).clamp(-1, 1).to(dev), torch.randn(B, 1, L, 4096, generator=g).to(dev), torch.ones(B, L, dtype=torch.int64), info
         while True:
-            yield torch.randn(B, 4, lat, lat, generator=g).to(dev), torch.randn(B, 1, L, 4096, generator=g).to(dev), torch.ones(B, L, dtype=torch.int64)
+            yield torch.randn(B, 4, lat, lat, generator=g).to(dev), torch.randn(B, 1, L, 4096, generator=g).to(dev), torch.ones(B, L, dtype=torch.int64), info
     names = sorted(glob.glob(os.path.join(cfg["data_root"], "*.npz")))[rank::world]
     while True:
         for i in range(0, len(names) - B + 1, B):
@@ -131,13 +102,13 @@ def batches(cfg, B, lat, L, dev, rank, world, synthetic):
                 zs.append(torch.from_numpy(mean + std * np.random.randn(*mean.shape)).float())
                 ys.append(torch.from_numpy(f["caption_feature"]).float().reshape(1, -1, 4096)[:, :L])
                 ms.append(torch.from_numpy(f["attention_mask"]).reshape(-1)[:L])
-            yield torch.stack(zs).to(dev), torch.stack(ys).to(dev), torch.stack(ms)
+            yield torch.stack(zs).to(dev), torch.stack(ys).to(dev), torch.stack(ms), info
 
 
 def load_config(path, debug=False):
     cfg = dict(DEFAULTS)
     if path:
-        user = _run_config(path)
+        user = run_config(path)
         unknown = sorted(k for k in user if k not in DEFAULTS and k not in IGNORED_KEYS and k not in SEMANTIC_KEYS and k != "data")
         if unknown:
             raise SystemExit(f"{path}: config keys this training path does not implement: {unknown} (supported: {sorted(DEFAULTS)})")
@@ -254,22 +225,108 @@ def load_optimizer_state(opt, sd, rank):
     return True
 
 
-def main():
-    a = parse_args()
-    cfg = load_config(a.config, a.debug)
-    cfg["mixed_precision"] = MIXED_PRECISION
+def init_process():
+    """(world, rank, device) from the launcher's environment; the nccl process group when there is more than one rank."""
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)
+    return world, rank, dev
+
+
+def build_denoiser(cfg):
+    return build_model(cfg["model"], cfg["grad_checkpointing"], cfg["fp32_attention"], gc_step=cfg["gc_step"], input_size=cfg["image_size"] // 8,
+                       pe_interpolation=cfg["image_size"] / 512, model_max_length=cfg["model_max_length"], micro_condition=cfg["micro_condition"],
+                       kv_compress_config=cfg["kv_compress_config"] if cfg["kv_compress"] else None,
+                       pred_sigma=cfg["pred_sigma"], learn_sigma=cfg["learn_sigma"], class_dropout_prob=cfg["class_dropout_prob"])
+
+
+def make_schedule(cfg, o, B, world, accum):
+    """Learning rate: batch-size scaling (reference train.py:448-452), which rewrites o["lr"], + warm-up schedule (lr_scheduler.py:10-40).
+    Returns (schedule, auto_lr ratio)."""
+    ratio = 1.0
+    if cfg["auto_lr"]:
+        o["lr"], ratio = auto_scale_lr(B * world * accum, o["lr"], **cfg["auto_lr"])
+    # accelerate steps the prepared scheduler `world` times per optimizer step (split_batches=False, the reference's setting): steps_per_call
+    sched = LRSchedule(o["lr"], cfg["lr_schedule"], lr_scale_ratio=ratio, steps_per_call=world,
+                       num_training_steps=(cfg["num_steps_per_epoch"] or 0) * cfg["num_epochs"] or None, **(cfg["lr_schedule_args"] or {}))
+    return sched, ratio
+
+
+def load_vae(cfg, dev):
+    """The VAE of the modes that train from pictures (reference train.py:351-354), whose scaling factor becomes cfg["scale_factor"]; None with feature files."""
+    if cfg["load_vae_feat"]:
+        return None
+    from pixart_sigma_amd.vae import AutoencoderKL
+    have = os.path.isdir(str(cfg["vae_pretrained"]))
+    vae = (AutoencoderKL.from_pretrained(cfg["vae_pretrained"], torch_dtype=torch.float16) if have else AutoencoderKL(scaling_factor=cfg["scale_factor"])).to(dev)
+    cfg["scale_factor"] = vae.config.scaling_factor
+    return vae
+
+
+def _scaled_latents(it, cfg, vae):
+    for z, y, mask, info in it:
+        if vae is not None:                                                        # reference train.py:147-153
+            z = vae.encode(z).latent_dist.sample().float()
+        yield z * cfg["scale_factor"], y, mask, info
+
+
+def data_source(cfg, synthetic, B, lat, L, dev, rank, world, vae):
+    """The batches of the config's data mode, every one (x0, y, mask, data_info) with x0 already times the scale factor.  Returns (iterator, the
+    CaptionEncoder to close or None)."""
+    if pictures_mode(cfg, synthetic):                                              # VAE, posterior kernel and scale factor inside the iterator
+        return picture_batches(cfg, B, L, dev, rank, world, vae)
+    use_ds = bool(cfg["data_root"]) and not synthetic and os.path.exists(os.path.join(cfg["data_root"], "data_info.json"))
+    it = feature_batches(cfg, B, L, dev, rank, world) if use_ds else batches(cfg, B, lat, L, dev, rank, world, synthetic)
+    return _scaled_latents(it, cfg, vae), None
+
+
+def train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, max_steps, save):
+    """Optimizer steps start_step + 1 ... start_step + max_steps (without end when max_steps is None), `save(step)` on rank 0 every save_model_steps.
+    Returns (last step, its loss as the log line prints it, still a tensor)."""
+    accum = int(cfg["gradient_accumulation_steps"])
+    t0, step = time.time(), start_step
+    sched_skips_seen = scaler.steps_skipped if scaler else 0
+    while max_steps is None or step < start_step + max_steps:
+        opt.zero_grad()
+        opt.lr = sched.lr
+        for micro in range(accum):                                                 # accelerator.accumulate (reference train.py:175)
+            x0, y, mask, info = next(it)
+            t = torch.randint(0, cfg["train_sampling_steps"], (x0.shape[0],), device=dev).long()
+            loss = diff.training_losses(model, x0, t, model_kwargs=dict(y=y, mask=mask, data_info=info))["loss"].mean() / accum
+            if micro + 1 < accum:
+                with opt.reducer.no_sync():                                        # local accumulation, no all-reduce yet
+                    (scaler.scale(loss) if scaler else loss).backward()
+            else:
+                (scaler.scale(loss) if scaler else loss).backward()
+        opt.step()
+        sched.step()
+        step += 1
+        saving = step % cfg["save_model_steps"] == 0
+        if scaler and (step % cfg["log_interval"] == 0 or saving):   # accelerate does not advance the schedule on a step the GradScaler skipped; the skip count
+            skipped = scaler.steps_skipped                     # lives on the device, so the schedule is reconciled where the host syncs anyway (skips are rare) -
+            sched.last_step -= world * (skipped - sched_skips_seen)   # and ALWAYS in front of a checkpoint: a resumed run starts its own count from the loaded
+            sched_skips_seen = skipped                         # scaler's total, so skips not yet subtracted at save time would never be (ADVICE r03)
+        if step % cfg["log_interval"] == 0 and rank == 0:      # host sync only here (the reference syncs every step, train.py:187)
+            extra = f" loss_scale {scaler.value:g} skipped {scaler.steps_skipped}" if scaler else ""
+            print(f"step {step} loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}{extra} "
+                  f"{(time.time() - t0) / cfg['log_interval']:.3f} s/step", flush=True)
+            t0 = time.time()
+        if saving and rank == 0:
+            save(step)
+    return step, loss.detach().double() * accum
+
+
+def main():
+    a = parse_args()
+    cfg = load_config(a.config, a.debug)
+    cfg["mixed_precision"] = MIXED_PRECISION
+    world, rank, dev = init_process()
     torch.manual_seed(cfg["seed"])
     lat, L, B, accum = cfg["image_size"] // 8, cfg["model_max_length"], cfg["train_batch_size"], int(cfg["gradient_accumulation_steps"])
-    model = build_model(cfg["model"], cfg["grad_checkpointing"], cfg["fp32_attention"], gc_step=cfg["gc_step"], input_size=lat,
-                        pe_interpolation=cfg["image_size"] / 512, model_max_length=L, micro_condition=cfg["micro_condition"],
-                        kv_compress_config=cfg["kv_compress_config"] if cfg["kv_compress"] else None,
-                        pred_sigma=cfg["pred_sigma"], learn_sigma=cfg["learn_sigma"], class_dropout_prob=cfg["class_dropout_prob"])
+    model = build_denoiser(cfg)
     start_step, sd = 0, None
     ck = a.resume_from or a.load_from
     if ck:
@@ -277,14 +334,8 @@ def main():
         model.load_state_dict(sd.get("state_dict", sd), strict=False)
     model = model.to(dev).train()
     model.prepare(dev)
-    # ---- learning rate: batch-size scaling (reference train.py:448-452) + warm-up schedule (lr_scheduler.py:10-40)
     o = dict(cfg["optimizer"])
-    ratio = 1.0
-    if cfg["auto_lr"]:
-        o["lr"], ratio = auto_scale_lr(B * world * accum, o["lr"], **cfg["auto_lr"])
-    # accelerate steps the prepared scheduler `world` times per optimizer step (split_batches=False, the reference's setting): steps_per_call
-    sched = LRSchedule(o["lr"], cfg["lr_schedule"], lr_scale_ratio=ratio, steps_per_call=world,
-                       num_training_steps=(cfg["num_steps_per_epoch"] or 0) * cfg["num_epochs"] or None, **(cfg["lr_schedule_args"] or {}))
+    sched, ratio = make_schedule(cfg, o, B, world, accum)
     scaler = LossScaler(dev) if cfg["mixed_precision"] == "fp16" else None      # GradScaler protocol of accelerate's fp16 mode, on the device
     if o.get("type", "AdamW") in ("CAMEWrapper", "CAME"):      # the optimizer of the PixArt-Sigma configs (reference optimizer.py:242-246)
         opt = FusedCAME(model, lr=o["lr"], weight_decay=o.get("weight_decay", 0.0), eps=o.get("eps", (1e-30, 1e-16)),
@@ -307,64 +358,19 @@ def main():
         print(f"lr {o['lr']:.3e} (auto_lr x{ratio:.3f}), schedule {cfg['lr_schedule']} {cfg['lr_schedule_args']}, accumulation {accum}, "
               f"operands {cfg['mixed_precision']}" + (f", loss scale {scaler.value:g}" if scaler else ""), flush=True)
     diff = IDDPM(str(cfg["train_sampling_steps"]), learn_sigma=cfg["learn_sigma"], pred_sigma=cfg["pred_sigma"], snr=cfg["snr_loss"])
-    vae = None
-    if not cfg["load_vae_feat"]:                                                   # reference train.py:351-354
-        from pixart_sigma_amd.vae import AutoencoderKL
-        have = os.path.isdir(str(cfg["vae_pretrained"]))
-        vae = (AutoencoderKL.from_pretrained(cfg["vae_pretrained"], torch_dtype=torch.float16) if have else AutoencoderKL(scaling_factor=cfg["scale_factor"])).to(dev)
-        cfg["scale_factor"] = vae.config.scaling_factor
+    vae = load_vae(cfg, dev)
     os.makedirs(os.path.join(a.work_dir, "checkpoints"), exist_ok=True)
-    use_ds = bool(cfg["data_root"]) and not a.synthetic and os.path.exists(os.path.join(cfg["data_root"], "data_info.json"))
-    pictures, captions = pictures_mode(cfg, a.synthetic), None
-    if pictures:                                                                   # x0 comes out of the iterator: VAE, posterior kernel and scale factor inside
-        it, captions = picture_batches(cfg, B, L, dev, rank, world, vae)
-        if rank == 0:
-            print(f"data: pictures of {picture_root(cfg)} with {'caption feature files' if cfg['load_t5_feat'] else 'text captions'}", flush=True)
-    else:
-        it = feature_batches(cfg, B, L, dev, rank, world) if use_ds else batches(cfg, B, lat, L, dev, rank, world, a.synthetic)
-    t0, step = time.time(), start_step
-    sched_skips_seen = scaler.steps_skipped if scaler else 0
-    while a.max_steps is None or step < start_step + a.max_steps:
-        opt.zero_grad()
-        opt.lr = sched.lr
-        for micro in range(accum):                                                 # accelerator.accumulate (reference train.py:175)
-            batch = next(it)
-            z, y, mask = batch[:3]
-            # micro-conditioning inputs (reference train.py:156): from the dataset, or the latent's own size for flat / synthetic data
-            info = batch[3] if len(batch) > 3 else {"img_hw": torch.tensor([[z.shape[-2] * 8.0, z.shape[-1] * 8.0]] * z.shape[0]),
-                                                    "aspect_ratio": torch.tensor([[z.shape[-2] / z.shape[-1]]] * z.shape[0])}
-            if pictures:
-                x0 = z
-            else:
-                if vae is not None:                                                # reference train.py:147-153
-                    z = vae.encode(z).latent_dist.sample().float()
-                x0 = z * cfg["scale_factor"]
-            t = torch.randint(0, cfg["train_sampling_steps"], (z.shape[0],), device=dev).long()
-            loss = diff.training_losses(model, x0, t, model_kwargs=dict(y=y, mask=mask, data_info=info))["loss"].mean() / accum
-            if micro + 1 < accum:
-                with opt.reducer.no_sync():                                        # local accumulation, no all-reduce yet
-                    (scaler.scale(loss) if scaler else loss).backward()
-            else:
-                (scaler.scale(loss) if scaler else loss).backward()
-        opt.step()
-        sched.step()
-        step += 1
-        saving = step % cfg["save_model_steps"] == 0
-        if scaler and (step % cfg["log_interval"] == 0 or saving):   # accelerate does not advance the schedule on a step the GradScaler skipped; the skip count
-            skipped = scaler.steps_skipped                     # lives on the device, so the schedule is reconciled where the host syncs anyway (skips are rare) -
-            sched.last_step -= world * (skipped - sched_skips_seen)   # and ALWAYS in front of a checkpoint: a resumed run starts its own count from the loaded
-            sched_skips_seen = skipped                         # scaler's total, so skips not yet subtracted at save time would never be
-        if step % cfg["log_interval"] == 0 and rank == 0:      # host sync only here (the reference syncs every step, train.py:187)
-            extra = f" loss_scale {scaler.value:g} skipped {scaler.steps_skipped}" if scaler else ""
-            print(f"step {step} loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}{extra} "
-                  f"{(time.time() - t0) / cfg['log_interval']:.3f} s/step", flush=True)
-            t0 = time.time()
-        if saving and rank == 0:
-            torch.save({"state_dict": model.state_dict(), "optimizer": opt.state_dict(), "lr_scheduler": sched.state_dict(), "step": step,
-                        **({"loss_scaler": scaler.state_dict()} if scaler else {})},
-                       os.path.join(a.work_dir, "checkpoints", f"epoch_1_step_{step}.pth"))
+    it, captions = data_source(cfg, a.synthetic, B, lat, L, dev, rank, world, vae)
+    if rank == 0 and pictures_mode(cfg, a.synthetic):
+        print(f"data: pictures of {picture_root(cfg)} with {'caption feature files' if cfg['load_t5_feat'] else 'text captions'}", flush=True)
+
+    def save(step):
+        torch.save({"state_dict": model.state_dict(), "optimizer": opt.state_dict(), "lr_scheduler": sched.state_dict(), "step": step,
+                    **({"loss_scaler": scaler.state_dict()} if scaler else {})},
+                   os.path.join(a.work_dir, "checkpoints", f"epoch_1_step_{step}.pth"))
+    step, loss = train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, a.max_steps, save)
     if rank == 0:
-        print(f"finished at step {step}: loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}", flush=True)
+        print(f"finished at step {step}: loss {loss.item():.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}", flush=True)
     if captions is not None:
         captions.close()
     if world > 1:
