@@ -246,6 +246,18 @@ int pxa_clip_coef_scaled(const float* sumsq, float* out2, float max_norm, float 
 int pxa_adamw_step_scaled(float* p, const float* g, float* m, float* v, void* p_bf16, long n, float lr, float beta1, float beta2,
                           float eps, float weight_decay, const float* gscale, const float* scaler, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- EMA of the weights
+ * The averaged weights a diffusion model is sampled from: the reference's ema_update(model_ema, model, ema_rate) behind optimizer.step() and the
+ * `state_dict_ema` of its checkpoints (diffusion/utils/checkpoint.py:11-20,45,62-63; ema_rate = 0.9999, configs/PixArt_xl2_internal.py), over the flat
+ * fp32 master buffer instead of a parameter-by-parameter loop and a second nn.Module.
+ * pxa_ema_update: per element  om = 1.f - decay;  ema = fmaf(om, p - ema, ema)  (p == ema returns ema bit for bit).  scaler: NULL, or the loss scaler's
+ * 5-float device record above - when scaler[2] != 0 (this step was skipped on overflow) nothing is written, so the EMA counts applied steps without a
+ * host synchronisation.  Refused: null pointers, n <= 0 or n % 4 != 0, pointers not 16-byte aligned, decay outside [0, 1), ema == p (or overlapping).
+ * pxa_swap_f32: exchanges two disjoint buffers in place (same n / alignment rules; overlapping ranges are refused): sampling from the EMA swaps it with
+ * the master, re-casts, samples and swaps back - no third full-size buffer.  Both move 16 bytes per thread per stream, grid-stride, nothing else. */
+int pxa_ema_update(float* ema, const float* p, long n, float decay, const float* scaler, hipStream_t stream);
+int pxa_swap_f32(float* a, float* b, long n, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------- fused diffusion loss
  * GaussianDiffusion.training_losses for IDDPM(learn_sigma=True, pred_sigma=True) = MSE + VB with the learned-range variance
  * (diffusion/model/gaussian_diffusion.py:744-855, :711-742, :280-361; diffusion_utils.py:10-88).  model_out (B, 2C, H, W), x0 / noise

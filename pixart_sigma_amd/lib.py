@@ -138,6 +138,8 @@ SIGNATURES = {
     "pxa_lora_bwd": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "pxa_image_resample": [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P],
     "pxa_image_to_u8": [_P, _I, _L, _I, _I, _P, _P],
+    "pxa_ema_update": [_P, _P, _L, _F, _P, _P],
+    "pxa_swap_f32": [_P, _P, _L, _P],
 }
 OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan", "pxa_attn_plan",
                  "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes", "pxa_vae_posterior",

@@ -383,6 +383,18 @@ def adamw_step(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, gs
     call("pxa_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), p.numel(), lr, beta1, beta2, eps, weight_decay, step, ptr(gscale))
 
 
+def ema_update(ema, p, decay, scaler_state=None):
+    """ema <- ema + (1 - decay) (p - ema) over two flat fp32 buffers; with the loss scaler's record, nothing is written on a skipped step (csrc/ema.hip)."""
+    assert ema.dtype == F32 and p.dtype == F32 and ema.numel() == p.numel() and ema.is_contiguous() and p.is_contiguous()
+    call("pxa_ema_update", ptr(ema), ptr(p), p.numel(), float(decay), ptr(scaler_state))
+
+
+def swap_f32(a, b):
+    """a <-> b, two disjoint flat fp32 buffers, in place."""
+    assert a.dtype == F32 and b.dtype == F32 and a.numel() == b.numel() and a.is_contiguous() and b.is_contiguous()
+    call("pxa_swap_f32", ptr(a), ptr(b), a.numel())
+
+
 def scale_copy(src, src_stride, nblocks, n_scaled, n_total, scale, out_bf16=None, out_f32=None):
     """nblocks strided blocks of a flat fp32 buffer -> (nblocks, n_total) copies whose first n_scaled elements carry `scale` (one rounding)."""
     out = out_bf16 if out_bf16 is not None else out_f32

@@ -57,6 +57,7 @@ def get_args():
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
     p.add_argument("--lora_path", default=None, type=str, help="peft-format adapter directory (adapter_config.json + adapter_model.safetensors) for the transformer blocks")
     p.add_argument("--lora_scale", default=1.0, type=float, help="multiplies the adapters' lora_alpha / r (0 = the base model)")
+    p.add_argument("--load_ema", action="store_true", help="with --model_path: sample from the checkpoint's state_dict_ema (written by train.py --ema)")
     p.add_argument("--save_images", default=None, choices=["png", "jpg"], help="also write one picture per sample (as the reference's save_image: output/<save_name>/<index>.<ext>)")
     return p.parse_args()
 
@@ -100,6 +101,15 @@ def encode_prompts(args, prompts, L):
     return out_dir
 
 
+def checkpoint_weights(sd, path, load_ema):
+    """The weights to sample from: state_dict (or the file itself), or with --load_ema the averaged ones."""
+    if not load_ema:
+        return sd.get("state_dict", sd)
+    if not isinstance(sd, dict) or "state_dict_ema" not in sd:
+        raise SystemExit(f"{path}: the checkpoint has no state_dict_ema (it was written without --ema): --load_ema cannot take its weights from it")
+    return sd["state_dict_ema"]
+
+
 @torch.no_grad()
 def main():
     args = get_args()
@@ -119,7 +129,9 @@ def main():
                           micro_condition=(args.version == "alpha" and args.image_size == 1024))
     if args.model_path:
         sd = torch.load(args.model_path, map_location="cpu")
-        model.load_state_dict(sd.get("state_dict", sd), strict=False)
+        model.load_state_dict(checkpoint_weights(sd, args.model_path, args.load_ema), strict=False)
+    elif args.load_ema:
+        raise SystemExit("--load_ema needs --model_path")
     if args.lora_path:                  # folded into the 16-bit operand weights when the model is prepared: the sampler runs the unchanged kernels
         lo = model.load_lora(args.lora_path, scale=args.lora_scale)
         print(f"LoRA adapters from {args.lora_path}: r={lo.config.r}, s={lo.scale:g}, {len(lo.params) // 2} adapted linears")

@@ -12,9 +12,15 @@ Data, chosen by the config (top-level `load_vae_feat` / `load_t5_feat`, else tho
     mixed_precision = 'fp16' the T5 encoder, which needs bf16 operands, runs in a worker process per rank (pixart_sigma_amd.t5.captions);
   * pictures and caption feature files (load_vae_feat = False, load_t5_feat = True).
 With `load_vae_feat = False` and `--synthetic` (or no data_root) the batches are noise images and the latents come from the HIP VAE on the fly
-(`vae_pretrained` = a diffusers AutoencoderKL directory; a random-init VAE when it is absent).  tensorboard/wandb trackers and validation image logging are
-outside this repo's scope: the config is a plain Python file (with mmcv's `_base_` inheritance) whose module-level names are the keys
-of section 5 of the survey.
+(`vae_pretrained` = a diffusers AutoencoderKL directory; a random-init VAE when it is absent).  tensorboard/wandb trackers are outside this repo's scope
+(SURVEY.md section 2): the config is a plain Python file (with mmcv's `_base_` inheritance) whose module-level names are the keys of section 5 of the survey.
+
+Opt-in, off by default (a run without these flags makes the launches and files it made before they existed):
+  * `--ema [--ema-rate X]`: an exponential moving average of the weights (pixart_sigma_amd.ema.WeightEMA) at the config's `ema_rate`, updated behind every
+    optimizer step and written as `state_dict_ema` beside `state_dict` (the reference's checkpoint layout); `--load-ema` starts from a checkpoint's
+    `state_dict_ema`;
+  * `--visualize`: validation pictures of the config's `validation_prompts` after step 1 and every `eval_sampling_steps` steps (reference train.py:45-103,
+    225-228) into `<work-dir>/validation/step_<n>[_ema]/<i>.png`; caption features from `--validation-feats DIR` or, with text captions, from the T5 encoder.
 """
 import argparse
 import glob
@@ -49,11 +55,15 @@ DEFAULTS = dict(model="PixArtMS_XL_2", image_size=1024, train_batch_size=16, num
                 vae_pretrained="output/pretrained_models/pixart_sigma_sdxlvae_T5_diffusers/vae",
                 # schedule / scaling keys of the reference configs (configs/PixArt_xl2_internal.py:34-57)
                 gradient_accumulation_steps=1, auto_lr=None, lr_schedule="constant", lr_schedule_args=dict(num_warmup_steps=0),
-                mixed_precision="bf16", aspect_ratio_type=None, valid_num=0, num_steps_per_epoch=None)
+                mixed_precision="bf16", aspect_ratio_type=None, valid_num=0, num_steps_per_epoch=None,
+                # read only under --ema / --visualize (the config keys alone switch nothing on, as in the reference's Sigma train.py, which keeps no EMA
+                # whatever ema_rate says): the EMA decay (0.9999 when None), the prompts of the validation pictures and the interval between them
+                ema_rate=None, validation_prompts=None, eval_sampling_steps=250)
 # keys of reference configs that name subsystems outside this path and cannot change what is trained: accepted and ignored.
 # Anything else that is not in DEFAULTS raises: a recognised-but-unsupported option must not silently change what is trained.
-IGNORED_KEYS = {"work_dir", "eval_sampling_steps", "visualize", "resume_from", "load_from",
-                "validation_prompts", "save_model_epochs", "window_block_indexes", "window_size", "use_rel_pos", "lewei_scale", "pe_interpolation", "roots",
+# `visualize`: every Sigma config sets it, so the key alone stays without effect - validation pictures are switched on by --visualize.
+IGNORED_KEYS = {"work_dir", "visualize", "resume_from", "load_from",
+                "save_model_epochs", "window_block_indexes", "window_size", "use_rel_pos", "lewei_scale", "pe_interpolation", "roots",
                 "tracker_project_name", "name", "num_ddim_timesteps", "w_max", "w_min", "cfg_scale", "eval_metric", "max_length",
                 # the rest of configs/PixArt_xl2_internal.py, which every PixArt-Sigma config inherits: validation, logging and storage settings, and two
                 # names (lora_rank, num_group_tokens) the reference's train.py never reads
@@ -61,8 +71,8 @@ IGNORED_KEYS = {"work_dir", "eval_sampling_steps", "visualize", "resume_from", "
 # keys that DO change what is trained and that this path implements for one value only: that value (or absence) is accepted, anything else refused
 # (real_prompt_ratio is checked in load_config: any value in [0, 1] when captions are text, 1.0 only with caption feature files).
 SEMANTIC_KEYS = {"qk_norm": (False,), "mask_loss_coef": (0.0, 0), "mask_type": ("null", None), "load_mask_index": (False,),
-                 "loss_type": (None, "mse", "l2", "huber"), "huber_c": None, "ema_rate": None, "ema_decay": None, "skip_step": (0,), "conditional_dropout": (False, None),
-                 "multi_scale": None, "use_fsdp": (False,)}      # None = any value: EMA is not kept, huber_c only matters under loss_type 'huber', multi_scale is the
+                 "loss_type": (None, "mse", "l2", "huber"), "huber_c": None, "ema_decay": None, "skip_step": (0,), "conditional_dropout": (False, None),
+                 "multi_scale": None, "use_fsdp": (False,)}      # None = any value: the EMA's decay is `ema_rate` (under --ema), huber_c only matters under loss_type 'huber', multi_scale is the
                                                                   # dataset class choice (the bucketed FeatureDatasetMS handles both); loss_type = 'huber' comes with
                                                                   # configs/PixArt_xl2_internal.py, the base of every Sigma config, and only train_pixart_lcm.py reads it:
                                                                   # the reference's train.py trains those configs with the IDDPM loss, as this one does
@@ -78,7 +88,83 @@ def parse_args():
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--max-steps", type=int, default=None)
     p.add_argument("--mixed-precision", choices=["fp16", "bf16"], default=None, help="overrides the config's mixed_precision")
+    add_ema_visualize_args(p)
+    p.add_argument("--load-ema", action="store_true", help="with --load-from / --resume-from: start from the checkpoint's state_dict_ema")
     return p.parse_args()
+
+
+def add_ema_visualize_args(p):
+    """The opt-in arguments train.py and train_lora.py share."""
+    p.add_argument("--ema", action="store_true", help="keep an EMA of the trained weights at the config's ema_rate (0.9999 without one)")
+    p.add_argument("--ema-rate", type=float, default=None, help="with --ema: overrides the config's ema_rate")
+    p.add_argument("--visualize", action="store_true", help="sample the config's validation_prompts after step 1 and every eval_sampling_steps steps")
+    p.add_argument("--validation-feats", default=None, help="with --visualize: directory of <idx>.npz + null.npz caption features, index = position in validation_prompts")
+
+
+def ema_decay(a, cfg):
+    """The EMA's decay, or None when no EMA is kept: --ema switches it on, then --ema-rate wins over the config's ema_rate, which wins over 0.9999."""
+    if not a.ema:
+        if a.ema_rate is not None:
+            raise SystemExit("--ema-rate needs --ema")
+        return None
+    d = a.ema_rate if a.ema_rate is not None else cfg.get("ema_rate")
+    d = 0.9999 if d is None else d
+    if not isinstance(d, (int, float)) or not 0 <= d < 1:
+        raise SystemExit(f"EMA rate {d!r} must lie in [0, 1)")
+    return float(d)
+
+
+def ema_weights_of(sd, path):
+    """--load-ema / --load_ema: the checkpoint's averaged weights."""
+    if not isinstance(sd, dict) or "state_dict_ema" not in sd:
+        raise SystemExit(f"{path}: the checkpoint has no state_dict_ema (it was written without --ema): --load-ema cannot take its weights from it")
+    return sd["state_dict_ema"]
+
+
+def check_visualize(a, cfg, text_captions):
+    """Start-up check of --visualize: the prompts, the interval and a source of caption features.  Returns the prompts ([] without --visualize)."""
+    if not a.visualize:
+        return []
+    prompts = cfg.get("validation_prompts")
+    if not prompts or not all(isinstance(s, str) for s in prompts):
+        raise SystemExit("--visualize: the config has no validation_prompts (a list of strings)")
+    k = cfg.get("eval_sampling_steps")
+    if not isinstance(k, int) or k < 1:
+        raise SystemExit(f"--visualize: eval_sampling_steps={k!r} must be a positive integer")
+    if not a.validation_feats and not text_captions:
+        raise SystemExit("--visualize needs the caption features of validation_prompts: give --validation-feats DIR (<idx>.npz + null.npz, as "
+                         "tools/extract_t5_features.py writes them), or train from text captions (load_t5_feat = False with a picture list and t5_path), "
+                         "where the T5 encoder makes them before the first step")
+    if a.validation_feats and not os.path.isdir(a.validation_feats):
+        raise SystemExit(f"--validation-feats {a.validation_feats}: not a directory")
+    return list(prompts)
+
+
+def validation_due(step, every):
+    """After step 1 and after every step divisible by eval_sampling_steps (reference train.py:225-228)."""
+    return step == 1 or step % every == 0
+
+
+def build_validation(a, cfg, model, vae, captions, dev, prompts):
+    """The ValidationSampler of --visualize; the VAE is loaded here when the data mode did not need one (reference train.py:84-85)."""
+    from pixart_sigma_amd.validation import ValidationSampler, load_validation_feats
+    L = cfg["model_max_length"]
+    if a.validation_feats:
+        feats, masks, null = load_validation_feats(a.validation_feats, len(prompts), L, dev)
+    else:
+        if captions.outstanding:
+            raise RuntimeError("validation prompts must be encoded before the first batch is requested")
+        y, m = [], []
+        for text in prompts + [""]:                                               # one at a time: the encoder's batch limit is the training batch's
+            f, k = captions.encode([text])
+            y.append(f.float().clone())
+            m.append(torch.as_tensor(k).reshape(1, -1).long().cpu())
+        feats, masks, null = torch.cat(y[:-1]), torch.cat(m[:-1]), y[-1]
+    if vae is None:
+        from pixart_sigma_amd.vae import AutoencoderKL
+        have = os.path.isdir(str(cfg["vae_pretrained"]))
+        vae = (AutoencoderKL.from_pretrained(cfg["vae_pretrained"], torch_dtype=torch.float16) if have else AutoencoderKL(scaling_factor=cfg["scale_factor"])).to(dev)
+    return ValidationSampler(model, vae, feats, masks, null, cfg["image_size"], os.path.join(a.work_dir, "validation"), seed=cfg["seed"])
 
 
 def batches(cfg, B, lat, L, dev, rank, world, synthetic):
@@ -283,9 +369,22 @@ def data_source(cfg, synthetic, B, lat, L, dev, rank, world, vae):
     return _scaled_latents(it, cfg, vae), None
 
 
-def train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, max_steps, save):
+def make_validate(a, cfg, model, vae, captions, dev, prompts, ema):
+    """validate(step) of train_loop: pictures from the raw weights, and from the EMA when one is kept."""
+    sampler = build_validation(a, cfg, model, vae, captions, dev, prompts)
+
+    def validate(step):
+        sampler.run(step)
+        if ema is not None:
+            sampler.run(step, ema=ema)
+        print(f"step {step}: validation pictures of {len(prompts)} prompts in {os.path.join(sampler.out_dir, f'step_{step}')}" + (" and ..._ema" if ema is not None else ""), flush=True)
+    return validate
+
+
+def train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, max_steps, save, ema=None, validate=None):
     """Optimizer steps start_step + 1 ... start_step + max_steps (without end when max_steps is None), `save(step)` on rank 0 every save_model_steps.
-    Returns (last step, its loss as the log line prints it, still a tensor)."""
+    ema: its update() runs directly behind every opt.step() (once per optimizer step, not per micro-batch).  validate: `validate(step)` on rank 0 after
+    step 1 and every eval_sampling_steps steps, behind the log line.  Returns (last step, its loss as the log line prints it, still a tensor)."""
     accum = int(cfg["gradient_accumulation_steps"])
     t0, step = time.time(), start_step
     sched_skips_seen = scaler.steps_skipped if scaler else 0
@@ -302,6 +401,8 @@ def train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start
             else:
                 (scaler.scale(loss) if scaler else loss).backward()
         opt.step()
+        if ema is not None:
+            ema.update()
         sched.step()
         step += 1
         saving = step % cfg["save_model_steps"] == 0
@@ -314,6 +415,9 @@ def train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start
             print(f"step {step} loss {loss.item() * accum:.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}{extra} "
                   f"{(time.time() - t0) / cfg['log_interval']:.3f} s/step", flush=True)
             t0 = time.time()
+        if validate is not None and rank == 0 and validation_due(step, cfg["eval_sampling_steps"]):
+            validate(step)
+            t0 = time.time()                                    # the pictures' time is not a training step's
         if saving and rank == 0:
             save(step)
     return step, loss.detach().double() * accum
@@ -323,6 +427,11 @@ def main():
     a = parse_args()
     cfg = load_config(a.config, a.debug)
     cfg["mixed_precision"] = MIXED_PRECISION
+    decay = ema_decay(a, cfg)
+    text_captions = pictures_mode(cfg, a.synthetic) and not cfg["load_t5_feat"]
+    prompts = check_visualize(a, cfg, text_captions)
+    if a.load_ema and not (a.resume_from or a.load_from):
+        raise SystemExit("--load-ema needs --load-from or --resume-from")
     world, rank, dev = init_process()
     torch.manual_seed(cfg["seed"])
     lat, L, B, accum = cfg["image_size"] // 8, cfg["model_max_length"], cfg["train_batch_size"], int(cfg["gradient_accumulation_steps"])
@@ -331,7 +440,7 @@ def main():
     ck = a.resume_from or a.load_from
     if ck:
         sd = torch.load(ck, map_location="cpu", weights_only=False)
-        model.load_state_dict(sd.get("state_dict", sd), strict=False)
+        model.load_state_dict(ema_weights_of(sd, ck) if a.load_ema else sd.get("state_dict", sd), strict=False)
     model = model.to(dev).train()
     model.prepare(dev)
     o = dict(cfg["optimizer"])
@@ -357,18 +466,31 @@ def main():
     if rank == 0:
         print(f"lr {o['lr']:.3e} (auto_lr x{ratio:.3f}), schedule {cfg['lr_schedule']} {cfg['lr_schedule_args']}, accumulation {accum}, "
               f"operands {cfg['mixed_precision']}" + (f", loss scale {scaler.value:g}" if scaler else ""), flush=True)
+    ema = None
+    if decay is not None:
+        from pixart_sigma_amd.ema import WeightEMA
+        ema = WeightEMA(model, decay, scaler=scaler)            # starts as a copy of the loaded weights
+        if a.resume_from and sd is not None and not a.load_ema:
+            if "state_dict_ema" in sd:
+                ema.load_state_dict(sd["state_dict_ema"])
+            elif rank == 0:
+                print(f"resume: {a.resume_from} has no state_dict_ema; the EMA starts from the loaded weights", flush=True)
+        if rank == 0:
+            print(f"EMA of the weights at rate {decay:g}", flush=True)
     diff = IDDPM(str(cfg["train_sampling_steps"]), learn_sigma=cfg["learn_sigma"], pred_sigma=cfg["pred_sigma"], snr=cfg["snr_loss"])
     vae = load_vae(cfg, dev)
     os.makedirs(os.path.join(a.work_dir, "checkpoints"), exist_ok=True)
     it, captions = data_source(cfg, a.synthetic, B, lat, L, dev, rank, world, vae)
     if rank == 0 and pictures_mode(cfg, a.synthetic):
         print(f"data: pictures of {picture_root(cfg)} with {'caption feature files' if cfg['load_t5_feat'] else 'text captions'}", flush=True)
+    validate = make_validate(a, cfg, model, vae, captions, dev, prompts, ema) if prompts and rank == 0 else None
 
     def save(step):
         torch.save({"state_dict": model.state_dict(), "optimizer": opt.state_dict(), "lr_scheduler": sched.state_dict(), "step": step,
+                    **({"state_dict_ema": ema.state_dict()} if ema is not None else {}),
                     **({"loss_scaler": scaler.state_dict()} if scaler else {})},
                    os.path.join(a.work_dir, "checkpoints", f"epoch_1_step_{step}.pth"))
-    step, loss = train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, a.max_steps, save)
+    step, loss = train_loop(cfg, model, diff, opt, sched, scaler, it, dev, rank, world, start_step, a.max_steps, save, ema=ema, validate=validate)
     if rank == 0:
         print(f"finished at step {step}: loss {loss.item():.4f} grad_norm {opt.last_norm.item():.4f} lr {opt.lr:.3e}", flush=True)
     if captions is not None:
