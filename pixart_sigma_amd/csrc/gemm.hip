@@ -609,9 +609,15 @@ __device__ __forceinline__ void mfma_abl16(f32x4 (&q)[4], bf16x8 b0, bf16x8 a0, 
 #define GEMM_STORE_OVERLAP 1   // next item's main loop starts over the draining epilogue stores (counted vmcnt); 0 = wait for them (A/B)
 #endif
 #ifndef GEMM_M16
-#define GEMM_M16 3          // bit per layout (1 NT, 2 NN, 4 TN): main loop on v_mfma_f32_16x16x32; a cleared bit keeps that layout on 32x32x16.  TN measured
-                            // 2-4 % SLOWER in the 16-row shape (its read phase - 24 transpose reads + ~39 address VALU per k-unit - no longer fits into the issue
-                            // slots 32 back-to-back 16-cycle MFMAs of the partner wave leave: 3 per MFMA instead of 7), so it stays on 32x32x16
+#define GEMM_M16 7          // bit per layout (1 NT, 2 NN, 4 TN): main loop on v_mfma_f32_16x16x32; a cleared bit keeps that layout on 32x32x16 (A/B partner: -DGEMM_M16=3).
+                            // TN first measured 2-4 % SLOWER in the 16-row shape: with frag16 re-deriving its addresses the main loop held 24 VALU per k-unit (15 in the
+                            // 32-row loop) next to 24 transpose reads, in the issue slots 32 back-to-back 16-cycle MFMAs of the partner wave leave (3 per MFMA, not 7),
+                            // and the instance spilled 22 registers.  With pinned lane addresses and offset fields (pair16s: 11 VALU per k-unit, 8 of them the DMA
+                            // pointers) it is the faster one: the four dW rows of the training step 65.7 -> 56.3 ms, the step 412.7-415.0 -> 403.8-406.1 ms in four
+                            // interleaved rounds (profiles/tn16_*).  The instances still spill 3 (plain) / 12 (paired) registers outside the main loop.
+#endif
+#ifndef GEMM_TN_ADDR
+#define GEMM_TN_ADDR 1      // 16-row TN main loop: fragment addresses as per-item lane constants + immediate offsets (0 = re-derived per k-unit by frag16; A/B builds)
 #endif
 #ifndef GEMM_NT_STORE
 #define GEMM_NT_STORE 0     // bf16 output rows of the persistent kernel as non-temporal stores (A/B builds)
@@ -719,6 +725,18 @@ __device__ __forceinline__ bf16x8 frag16(const char* lds, int rbase, int lane, i
   }
 }
 
+// Byte offset, inside a k-strided image, of the first of frag16<false>'s two transpose reads (the second one lies 4 k-rows = 4 << (rows_log2 + 1) bytes
+// further on: (kr + 4) & 3 == kr & 3).  For rbase = r0 + 16 j with r0 a multiple of 64 (j < 4) or of 128 (j < 8), j only enters through the block index
+// (r0 >> 5 | j >> 1, XORed with kr & 3) and through bit 5 of the in-block offset (j & 1, XORed with bit 0 of the lane group): the offset of fragment j is
+// the offset of fragment 0 with j XORed into bits 5..7, whatever the lane.  So a lane's fragment addresses are item constants and ring slot, second read and
+// image origin are compile-time distances from them (tests/test_gemm_tn_addr_host.py restates and checks this for every lane, slot, fragment and image).
+__device__ __forceinline__ int frag16_tr_off(int rbase, int lane, int rows_log2) {
+  const int gg = lane >> 4, tt = lane & 15;
+  const int kr = 8 * gg + (tt >> 2), col = rbase + (tt & 3) * 4;
+  const int blk = col >> 5, inblk = ((col & 31) * 2) ^ ((gg & 1) << 5);
+  return (kr << (rows_log2 + 1)) + ((blk ^ (kr & 3)) << 6) + inblk;
+}
+
 // EPI (bf16 epilogue flavour, compiled separately so that none carries the others' registers - the epilogue runs with all
 // 128 accumulators live and spills at the slightest extra state): 0 = (+bias), 1 = act 3 (bias + GELU, GELU' as the second
 // output), 2 = act 4 (x aux) + bias-gradient column sums, 3 = everything decided at run time (acts 1 / 2 and odd mixes), 7 = act 1 (bias + GELU,
@@ -766,7 +784,8 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
   // owns 4 consecutive columns of one output row (lane (R, c): row 16 im + c, columns 16 jn + 4 R + g).  Fragment counts per k-unit are those of
   // the 32-row form: 12 ds_read_b128 (k-contiguous operands) or transpose-read pairs (k-strided), each now the unit's whole depth of 32.
   constexpr bool M16 = ((GEMM_M16 >> LAYOUT) & 1) && !(GEMM_ABL & 4);
-  constexpr int UNIT = 40960;                          // ring slot: A image at 0 (16 KiB; 32 KiB paired), B image behind it (16 KiB; 8 KiB paired)
+  constexpr bool TNA = GEMM_TN_ADDR && LAYOUT == 2 && M16 && PH16;     // address-free read phase (pair16s below)
+  constexpr int UNIT = 40960;                         // ring slot: A image at 0 (16 KiB; 32 KiB paired), B image behind it (16 KiB; 8 KiB paired)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 2, wn = wave & 3, hi = lane >> 5;
   const bool late = wave >= NW / 2;
@@ -927,7 +946,7 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
     const long k0 = (long)z_ * p.k_per_split;
     const bool vq = PAIR && vt, hq = HALF && vt;
     const int rla = vq ? 9 : 8, rlb = (vq || hq) ? 7 : 8;   // log2 of the A / B image row (column) counts
-    const int ln = opaque<LAYOUT == 1 || (EPI >= 2 && EPI != 7) || (GEMM_EPI_EARLY && RM == 2)>(lane);
+    const int ln = opaque<LAYOUT == 1 || (LAYOUT == 2 && M16) || (EPI >= 2 && EPI != 7) || (GEMM_EPI_EARLY && RM == 2)>(lane);
 #pragma unroll
     for (int i = 0; i < 5; i++) {
       const int id = wave + NW * i;                    // full tile: 16 A + 16 B pieces; paired: 32 A + 8 B
@@ -979,6 +998,16 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
     const int mw = hfc ? m0a + a_rb : ((vtc && (wn >> 1)) ? m0b : m0a) + wm * 128, nw = n0 + b_rb;   // this wave's output origin
     const int tm_eff = hfc ? 2 : TM;                    // row tiles of this wave's output
     const int zw = z_;                                  // this item's k-slice (fp32 slab index)
+    // TNA: this lane's 8 + 4 fragment addresses in ring slot 0, formed once per item (frag16_tr_off) and pinned in registers; pair16s reaches slot, second
+    // transpose read and the paired geometry through constants, the half of the ring through one scalar
+    int fa[8], fb[4];
+    if constexpr (TNA) {
+      const int wa = frag16_tr_off(a_rb, lane, rla), wb = boff + frag16_tr_off(b_rb, lane, rlb);
+#pragma unroll
+      for (int i = 0; i < 8; i++) { fa[i] = wa ^ (i << 5); asm volatile("" : "+v"(fa[i])); }
+#pragma unroll
+      for (int j = 0; j < 4; j++) { fb[j] = wb ^ (j << 5); asm volatile("" : "+v"(fb[j])); }
+    }
     PXA_TR(0);
     // This item's first units (and the cursor fetch) have landed once only the previous item's epilogue stores - issued after them, and
     // vmcnt retires in issue order - are still in flight: interior tiles of the plain / dual-output bf16 epilogues issue exactly
@@ -1159,6 +1188,61 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
         PXA_SB(); __builtin_amdgcn_s_barrier(); PXA_SB();
       }
     };
+    // unit16 of the 16-row TN instances, two units at a time: nk is even (k ranges are multiples of 64), so units 2 q, 2 q + 1 sit in ring slots 2 (q & 1) and
+    // 2 (q & 1) + 1.  A pair adds its half of the ring (0 or 2 UNIT, a scalar) to the 12 pinned lane addresses once; second slot, second transpose read and the
+    // paired flag VT are compile-time and ride in the reads' offset fields (at most 40960 + 4096 < 2^16).  DMA issue, counted waits and barriers are unit16's.
+    auto pair16s = [&](int roff, auto rem_c, auto vt_c) {
+      constexpr int REM0 = decltype(rem_c)::value;       // units that follow the pair's FIRST unit (>= 4: steady state)
+      constexpr bool VT = decltype(vt_c)::value != 0;
+      constexpr int AE = 4 << ((VT ? 9 : 8) + 1), BE = 4 << ((VT ? 7 : 8) + 1);
+      const char* qa[2 * TM];
+      const char* qb[2 * TN];
+#pragma unroll
+      for (int i = 0; i < 2 * TM; i++) qa[i] = smem + (fa[i] + roff);
+#pragma unroll
+      for (int j = 0; j < 2 * TN; j++) qb[j] = smem + (fb[j] + roff);
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        const int REM = REM0 - u, SO = u * UNIT;
+        bf16x8 bq[2 * TN], aq[2 * TM];
+#pragma unroll
+        for (int j = 0; j < 2 * TN; j++) bq[j] = concat_tr(lds_tr_read(qb[j] + SO), lds_tr_read(qb[j] + (SO + BE)));
+#pragma unroll
+        for (int i = 0; i < 2 * TM; i++) aq[i] = concat_tr(lds_tr_read(qa[i] + SO), lds_tr_read(qa[i] + (SO + AE)));
+        if (REM >= 3) {
+          // issue_lo + issue_hi of the unit three further on, into the slot behind this one: (roff ^ 2 UNIT) + UNIT for the pair's first unit, roff for its
+          // second.  Spelled out with the slot offset read into a scalar register: with s_lo / s_hi the compiler, out of scalar registers in this instance, kept
+          // the slot in a VECTOR register and handed that to the DMA's `s_mov_b32 m0` (an operand the instruction cannot take)
+          const int ds = __builtin_amdgcn_readfirstlane(u == 0 ? (roff ^ (2 * UNIT)) + UNIT : roff);
+#pragma unroll
+          for (int i = 0; i < (VT ? 5 : 4); i++) {
+            dma_count++;
+            lds_dma16(pp[i], smem + ds + dof[i]);
+#if !(GEMM_ABL & 1)
+            pp[i] += st[i];
+#endif
+          }
+        }
+        if (REM >= 3) { if (VT) wait_vmcnt<10>(); else wait_vmcnt<8>(); }
+        else if (REM == 2) { if (VT) wait_vmcnt<5>(); else wait_vmcnt<4>(); }
+        else if (REM == 1) wait_vmcnt<0>();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        PXA_SB(); __builtin_amdgcn_s_barrier(); PXA_SB();
+        if (GEMM_M16_PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 2 * TM; i++)
+#pragma unroll
+          for (int j = 0; j < 2 * TN; j++) acc4[i][j] = mfma16(bq[j], aq[i], acc4[i][j]);
+        if (GEMM_M16_PRIO) __builtin_amdgcn_s_setprio(0);
+        PXA_SB(); __builtin_amdgcn_s_barrier(); PXA_SB();
+      }
+    };
+    auto run_units_tn = [&](auto vt_c) {                 // REM per unit as in run_units: 3 while at least three units follow, then 2, 1, 0 (nk == 2: 1, 0)
+      int left = nk, roff = 0;
+      for (; left >= 6; left -= 2, roff ^= 2 * UNIT) pair16s(roff, IntC<4>{}, vt_c);
+      if (left == 4) { pair16s(roff, IntC<3>{}, vt_c); roff ^= 2 * UNIT; }
+      pair16s(roff, IntC<1>{}, vt_c);
+    };
     auto unit = [&](int t, auto rem_c, auto th_c) {
       if constexpr (PH16) unit16(t, rem_c, th_c); else unit8(t, rem_c, th_c);
     };
@@ -1169,7 +1253,9 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
       unit(t++, IntC<1>{}, th_c);
       unit(t++, IntC<0>{}, th_c);
     };
-    if (HALF && hfc) run_units(IntC<1>{}); else run_units(IntC<2>{});
+    if constexpr (TNA && PAIR) { if (vtc) run_units_tn(IntC<1>{}); else run_units_tn(IntC<0>{}); }
+    else if constexpr (TNA) run_units_tn(IntC<0>{});
+    else if (HALF && hfc) run_units(IntC<1>{}); else run_units(IntC<2>{});
 #if GEMM_ABL & 4
 #pragma unroll
     for (int i = 0; i < TM; i++)
@@ -1211,7 +1297,7 @@ __global__ __launch_bounds__(512) void gemm_pers_kernel(GemmParams p) {
                                                        // NOT in the count: wave 0 / lane 0's cursor atomic (fetch_issue, issued BEHIND the prefetch): one more operation
                                                        // in flight for that wave only, so its waits are conservative by one - never the other way.
     };
-    const int le = opaque<LAYOUT == 1 || (EPI >= 2 && EPI != 7) || (GEMM_EPI_EARLY && RM == 2)>(lane);          // NN: epilogue-only lane constants are rebuilt per item (see opaque())
+    const int le = opaque<LAYOUT == 1 || (LAYOUT == 2 && M16) || (EPI >= 2 && EPI != 7) || (GEMM_EPI_EARLY && RM == 2)>(lane);          // NN: epilogue-only lane constants are rebuilt per item (see opaque())
     const int srow = le & 31;
     if constexpr (LAYOUT == 2) {
       hand_over();
