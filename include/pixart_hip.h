@@ -425,6 +425,39 @@ int pxa_gemm_w8(const pxa_gemm_w8_args* args, hipStream_t stream);
 int pxa_gemm_w8_plan(const pxa_gemm_w8_args* args, char* out, int out_len);
 int pxa_gemm_w8_max_m(void);
 
+/* MXFP8 for the denoiser's inference path (csrc/gemm_f8.hip): both GEMM operands in FP8 on the block-scaled K = 128 MFMA.  A matrix X [R][K], K a multiple of 32,
+ * is held as q [R][K], one OCP e4m3fn byte per element with row pitch ldq bytes, and e [R][K / 32], one E8M0 byte per block of 32 consecutive k with row pitch lde
+ * bytes: X ~ q * 2^(e - 127).
+ * pxa_mx_quant_rows: src [R][K] with row pitch ld, in the operand type or (src_is_f32) fp32.  Per block: X = ceil(log2(amax / 448)), 0 for an all-zero block,
+ *   clamped to [-127, 127]; e = X + 127 (the E8M0 NaN code 0xFF is never written); q = e4m3fn(src / 2^X), the quotient exact, round to nearest even.  Nothing is
+ *   clipped (amax / 2^X <= 448) and the NaN codes 0x7F / 0xFF are never written.  Block-local: no row reduction.
+ * pxa_mx_dequant_rows: dst16[r][k] = q[r][k] * 2^(e[r][k / 32] - 127) in the operand type, row pitch ld: exact in bf16, and in fp16 where the value is normal.
+ * Both: K a multiple of 32; ld >= K and a multiple of 8 (elements); ldq >= K and a multiple of 16; lde >= K / 32; the 16-bit / fp32 matrix and q 16-byte aligned. */
+int pxa_mx_quant_rows(const void* src, int src_is_f32, long ld, long R, int K, void* q, long ldq, void* e, long lde, hipStream_t stream);
+int pxa_mx_dequant_rows(const void* q, long ldq, const void* e, long lde, long R, int K, void* dst16, long ld, hipStream_t stream);
+/* pxa_gemm_f8: C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (NT), A = (qa, ea) [M][K] and W = (qw, ew) [N][K] in the format above; both block scales go through
+ * the scale operands of v_mfma_scale_f32_16x16x128_f8f6f4, the sum is fp32.  bias fp32 [N] or NULL; act 0 = none, 1 = GELU(tanh) (pxa_gemm's codes).  Outputs, at
+ * least one:  out16 (operand type, pitch ld_out elements), the value rounded once;  out_q / out_e (together; pitches ld_outq, ld_oute bytes), that same
+ * 16-bit-rounded value quantised along n by pxa_mx_quant_rows' rule - bit for bit what pxa_mx_quant_rows gives on out16.
+ * Any M >= 1; N and K multiples of 128.  q pitches >= K (ld_outq >= N) and multiples of 16 bytes, ld_out >= N and a multiple of 8; qa, qw, bias, out16 and out_q
+ * 16-byte aligned.  The four scales of a row and a 128-deep step are read as one dword: e pitches >= K / 32 (ld_oute >= N / 32) and multiples of 4 bytes, ea, ew and
+ * out_e 4-byte aligned.  No K split, no atomics, no workspace: two calls on the same inputs give the same bits.  Every limit is checked before any HIP call (-1 and
+ * pxa_last_error).  pxa_gemm_f8_plan: the same checks with the same return codes and, for a call that would launch, one line of text
+ * "<kernel instance> mfma=.. split=1 bm=.. bn=.. bk=.. m_tiles=.. n_tiles=.. grid=.." (no GPU needed; pointers are only tested for NULL and alignment). */
+typedef struct {
+  const void* qa; long ldqa;
+  const void* ea; long ldea;
+  const void* qw; long ldqw;
+  const void* ew; long ldew;
+  int M, N, K, act;
+  const float* bias;
+  void* out16; long ld_out;
+  void* out_q; long ld_outq;
+  void* out_e; long ld_oute;
+} pxa_gemm_f8_args;
+int pxa_gemm_f8(const pxa_gemm_f8_args* args, hipStream_t stream);
+int pxa_gemm_f8_plan(const pxa_gemm_f8_args* args, char* out, int out_len);
+
 /* ---------------------------------------------------------------------------------------------- LoRA adapters
  * y = x (W + s B A)^T + b with A [r][K], B [N][r] stored transposed as Bt [r][N]: what peft's LoraLayer computes for the reference's fine-tuning scripts
  * (train_scripts/train_pixart_lora_hf.py:505-524).  The adapter is folded into the 16-bit operand copy of W, so every forward / dX GEMM runs unchanged;

@@ -1,0 +1,384 @@
+// MXFP8 (OCP MX, e4m3fn elements with one E8M0 scale per 32 consecutive k) for the denoiser's inference path: the block quantiser, its inverse, and an NT GEMM on
+// the block-scaled K = 128 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4), the only FP8 form of gfx950 that runs at twice the 16-bit matrix rate.
+//
+// Format.  A matrix X (R, K), K % 32 == 0, is held as q (R, K), one e4m3fn byte per element with row pitch ldq bytes, and e (R, K / 32), one E8M0 byte per block with
+// row pitch lde bytes: X ~ q * 2^(e - 127).  The quantiser keeps the rule of gemm_w8.hip per block instead of per row: the exponent is
+// ceil(log2(amax_block / 448)), 0 for an all-zero block, clamped to [-127, 127] (so the E8M0 NaN code 0xFF is never written), computed on the bits of amax
+// (exponent E, mantissa f: amax / 448 = (f / 1.75) 2^(E - 8), so it is E - 8, or E - 7 where f > 1.75; no logarithm is evaluated); q = e4m3fn(x / 2^X), the quotient
+// exact (v_ldexp_f32), round to nearest even.  amax / 2^X <= 448, so nothing is clipped; the clamp to +-448 in front of the conversion only keeps a non-finite
+// input from producing the NaN codes 0x7F / 0xFF.  q * 2^(e - 127) is exactly representable in bf16, and in fp16 wherever it is a normal number.
+//
+// pxa_gemm_f8: C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]), A = (qa, ea) (M, K), W = (qw, ew) (N, K).  Both block scales go through the instruction's scale
+// operands.  Lane maps of the instruction, measured on the MI355X with exact data and per-block scales (tests/test_gemm_f8_gpu.py): lane l = (t, g) = (l & 15, l >> 4)
+// holds row t of its operand; registers 0 .. 3 are k = 16 g .. 16 g + 15 and registers 4 .. 7 are k = 64 + 16 g .. 64 + 16 g + 15 of the 128-deep step (NOT 32
+// consecutive k); its scale byte is the scale of row t and k-block g (k = 32 g .. 32 g + 31) - the block that lanes (t, 2 (g & 1)) and (t, 2 (g & 1) + 1) hold in
+// register half g >> 1.
+//
+// Decomposition.  A workgroup of 4 waves (2 x 2) owns a 128 x 128 tile, a wave 64 x 64 of it as 4 x 4 MFMA tiles; one k-chunk is 128 bytes = one full line per row
+// and one MFMA step.  Both operand tiles go through LDS in full lines (16-byte pieces, eight consecutive lanes per row; row pitch 144 bytes), staged in registers
+// one chunk ahead: the loads of chunk c + 1 are issued before the MFMAs of chunk c and written to the single LDS buffer between two barriers after them.  The
+// four scale bytes of a row and chunk are one dword (lde % 4 == 0): 256 threads fetch the 128 + 128 dwords of a chunk into LDS with the tiles, and a lane takes byte
+// l >> 4 of its row's dword; its two 16-byte fragment halves are read at bytes 16 g and 64 + 16 g of its row.  The product is issued transposed (a = W fragment, b = A fragment), so a lane owns 4 consecutive columns of one row: 8-byte 16-bit
+// stores, one float4 of bias, and a 32-column block of a row lies in two MFMA tiles of one wave on the four lanes that share l & 15 - the fused MX output takes
+// its block maximum with two lane exchanges and no LDS.
+// No K split: every output element is summed by one lane in one fixed order, so two launches give the same bits; no atomics, no workspace.  Rows at or past M are
+// clamped at the load (nothing outside the operands is read) and not stored; N % 128 == 0 and K % 128 == 0, so there is no other edge.
+#include "common.h"
+#include "../../include/pixart_hip.h"
+
+#include <cstdio>
+
+namespace {
+using namespace pxa;
+
+constexpr int F8_BM = 128, F8_BN = 128, F8_BK = 128;
+constexpr int F8_PITCH = F8_BK + 16;                     // bytes of an LDS row of either tile
+constexpr int F8_TILE = F8_BM * F8_PITCH;
+constexpr int F8_LDS = 2 * F8_TILE + 2 * 128 * 4;         // A tile, W tile, 128 + 128 scale dwords
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// ------------------------------------------------------------------------------------------------ the rule
+// X = ceil(log2(amax / 448)) from the bits of amax (448 = 1.75 * 2^8), 0 for amax == 0, clamped to [-127, 127].  A subnormal amax reads E = -127 and lands on the
+// lower clamp, where its true exponent (below -134) lands as well.
+__device__ __forceinline__ int mx_exponent(float amax) {
+  const uint32_t bits = __builtin_bit_cast(uint32_t, amax) & 0x7fffffffu;
+  int x = (int)(bits >> 23) - 127 - 8 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  x = min(max(x, -127), 127);
+  return bits == 0 ? 0 : x;
+}
+// four values / 2^X -> four e4m3fn bytes
+__device__ __forceinline__ uint32_t mx_codes4(float a, float b, float c, float d, int x) {
+  const float v0 = fminf(fmaxf(__builtin_ldexpf(a, -x), -448.f), 448.f), v1 = fminf(fmaxf(__builtin_ldexpf(b, -x), -448.f), 448.f);
+  const float v2 = fminf(fmaxf(__builtin_ldexpf(c, -x), -448.f), 448.f), v3 = fminf(fmaxf(__builtin_ldexpf(d, -x), -448.f), 448.f);
+  int r = __builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false);
+  r = __builtin_amdgcn_cvt_pk_fp8_f32(v2, v3, r, true);
+  return (uint32_t)r;
+}
+
+template <bool F32>
+__device__ __forceinline__ void mx_load16(const void* src, long off, float (&f)[16]) {
+  if (F32) {
+    const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src) + off);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const float4 v = p[i]; f[4 * i] = v.x; f[4 * i + 1] = v.y; f[4 * i + 2] = v.z; f[4 * i + 3] = v.w; }
+  } else {
+    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(src) + off);
+    float lo[8], hi[8];
+    unpack_bf16x8(p[0], lo);
+    unpack_bf16x8(p[1], hi);
+#pragma unroll
+    for (int i = 0; i < 8; i++) { f[i] = lo[i]; f[8 + i] = hi[i]; }
+  }
+}
+
+// Two adjacent lanes per block, 16 elements each: one sweep, block-local.  The number of 16-element pieces is even (K % 32 == 0), so the two lanes of a block
+// are inside the loop together.
+template <bool F32>
+__global__ __launch_bounds__(256) void mx_quant_rows_kernel(const void* __restrict__ src, long ld, long R, int K, uint8_t* __restrict__ q, long ldq,
+                                                            uint8_t* __restrict__ e, long lde) {
+  const long per_row = K / 16, total = R * per_row;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / per_row;
+    const int c = (int)(i - r * per_row) * 16;
+    float f[16];
+    mx_load16<F32>(src, r * ld + c, f);
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; j++) amax = fmaxf(amax, fabsf(f[j]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1));
+    const int x = mx_exponent(amax);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) w[j] = mx_codes4(f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3], x);
+    *reinterpret_cast<uint4*>(q + r * ldq + c) = make_uint4(w[0], w[1], w[2], w[3]);
+    if ((c & 16) == 0) e[r * lde + (c >> 5)] = (uint8_t)(x + 127);
+  }
+}
+
+// dst[r][k] = q[r][k] * 2^(e[r][k / 32] - 127), exact: 16 bytes in, 32 bytes out per thread and step.
+__global__ __launch_bounds__(256) void mx_dequant_rows_kernel(const uint8_t* __restrict__ q, long ldq, const uint8_t* __restrict__ e, long lde, long R, int K,
+                                                              bf16_t* __restrict__ dst, long ld) {
+  const long per_row = K / 16, total = R * per_row;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / per_row;
+    const int c = (int)(i - r * per_row) * 16;
+    const int x = (int)e[r * lde + (c >> 5)] - 127;
+    const uint4 v = *reinterpret_cast<const uint4*>(q + r * ldq + c);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t o[8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
+      o[2 * j] = pack_bf16x2(__builtin_ldexpf(a[0], x), __builtin_ldexpf(a[1], x));
+      o[2 * j + 1] = pack_bf16x2(__builtin_ldexpf(b[0], x), __builtin_ldexpf(b[1], x));
+    }
+    uint4* d = reinterpret_cast<uint4*>(dst + r * ld + c);
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ the GEMM
+struct F8Params {
+  const uint8_t* qa; long ldqa; const uint8_t* ea; long ldea;
+  const uint8_t* qw; long ldqw; const uint8_t* ew; long ldew;
+  int M, N, K;
+  const float* bias;
+  bf16_t* out16; long ld_out;
+  uint8_t* out_q; long ld_outq; uint8_t* out_e; long ld_oute;
+  int m_tiles, n_tiles;
+};
+
+// a thread's staging set for one chunk: four 16-byte pieces of each tile and one scale dword.  Native vectors (see gemm_w8.hip: A4).
+struct F8Stage { nt_u4 a0, a1, a2, a3, w0, w1, w2, w3; uint32_t sc; };
+
+template <bool GELU, bool OUT16, bool OUTQ>
+__global__ __launch_bounds__(256) void gemm_f8_kernel(const F8Params p) {
+  __shared__ __attribute__((aligned(16))) char smem[F8_LDS];
+  // id -> (row tile, column tile): XCD id & 7 takes row tiles x, x + 8, ... and walks the column tiles of one row tile first, so the row tile's A lines and the
+  // whole weight matrix (1.3 - 5.3 MB) are re-read from that XCD's L2.  The rows, not the 9 / 27 / 36 column tiles of the model's GEMMs, are what divides by 8.
+  const int bid = blockIdx.x, r8 = bid >> 3;
+  const int mt = (r8 / p.n_tiles) * 8 + (bid & 7), nt = r8 % p.n_tiles;
+  if (mt >= p.m_tiles) return;                                       // the whole workgroup: no barrier is left behind
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int t = lane & 15, g = lane >> 4, wm = wave >> 1, wn = wave & 1;
+  const int m0 = mt * F8_BM, n0 = nt * F8_BN;
+  const int M = p.M;
+  char* const sA = smem;
+  char* const sW = smem + F8_TILE;
+  uint32_t* const sS = reinterpret_cast<uint32_t*>(smem + 2 * F8_TILE);
+
+  // staging: 128 rows x 8 pieces per tile; thread takes pieces tid + 256 i: row (tid >> 3) + 32 i, piece tid & 7
+  const int pc = tid & 7;
+  const uint8_t *a_src[4], *w_src[4];
+  int dst[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int row = (tid >> 3) + 32 * i;
+    a_src[i] = p.qa + (long)min(m0 + row, M - 1) * p.ldqa + pc * 16;
+    w_src[i] = p.qw + (long)(n0 + row) * p.ldqw + pc * 16;
+    dst[i] = row * F8_PITCH + pc * 16;
+  }
+  // scale dwords: threads 0 .. 127 the A rows, 128 .. 255 the W rows
+  const uint8_t* s_src = tid < 128 ? p.ea + (long)min(m0 + tid, M - 1) * p.ldea : p.ew + (long)(n0 + tid - 128) * p.ldew;
+
+  auto load = [&](int c, F8Stage& s) {
+    const long k = (long)c * F8_BK;
+    s.a0 = *reinterpret_cast<const nt_u4*>(a_src[0] + k);
+    s.a1 = *reinterpret_cast<const nt_u4*>(a_src[1] + k);
+    s.a2 = *reinterpret_cast<const nt_u4*>(a_src[2] + k);
+    s.a3 = *reinterpret_cast<const nt_u4*>(a_src[3] + k);
+    s.w0 = *reinterpret_cast<const nt_u4*>(w_src[0] + k);
+    s.w1 = *reinterpret_cast<const nt_u4*>(w_src[1] + k);
+    s.w2 = *reinterpret_cast<const nt_u4*>(w_src[2] + k);
+    s.w3 = *reinterpret_cast<const nt_u4*>(w_src[3] + k);
+    s.sc = *reinterpret_cast<const uint32_t*>(s_src + 4 * c);
+  };
+  auto store = [&](const F8Stage& s) {
+    *reinterpret_cast<nt_u4*>(sA + dst[0]) = s.a0;
+    *reinterpret_cast<nt_u4*>(sA + dst[1]) = s.a1;
+    *reinterpret_cast<nt_u4*>(sA + dst[2]) = s.a2;
+    *reinterpret_cast<nt_u4*>(sA + dst[3]) = s.a3;
+    *reinterpret_cast<nt_u4*>(sW + dst[0]) = s.w0;
+    *reinterpret_cast<nt_u4*>(sW + dst[1]) = s.w1;
+    *reinterpret_cast<nt_u4*>(sW + dst[2]) = s.w2;
+    *reinterpret_cast<nt_u4*>(sW + dst[3]) = s.w3;
+    sS[tid] = s.sc;
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nchunks = p.K / F8_BK;
+  F8Stage st;
+  load(0, st);
+  store(st);
+  __syncthreads();
+
+  // lane (t, g) of MFMA tile i (rows) / j (columns): row 16 i + t of the wave's 64, bytes 16 g .. 16 g + 15 and 64 + 16 g .. 64 + 16 g + 15 of the chunk
+  const int a_off = (wm * 64 + t) * F8_PITCH + 16 * g, w_off = (wn * 64 + t) * F8_PITCH + 16 * g;
+  for (int c = 0; c < nchunks; c++) {
+    load(min(c + 1, nchunks - 1), st);                                // past the last chunk: the last one again, never used
+    i32x8 af[4];
+    int sa[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const nt_u4 lo = *reinterpret_cast<const nt_u4*>(sA + a_off + i * 16 * F8_PITCH), hi = *reinterpret_cast<const nt_u4*>(sA + a_off + i * 16 * F8_PITCH + 64);
+      af[i] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+      sa[i] = (int)((sS[wm * 64 + 16 * i + t] >> (8 * g)) & 0xffu);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const nt_u4 lo = *reinterpret_cast<const nt_u4*>(sW + w_off + j * 16 * F8_PITCH), hi = *reinterpret_cast<const nt_u4*>(sW + w_off + j * 16 * F8_PITCH + 64);
+      const i32x8 wf = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+      const int sw = (int)((sS[128 + wn * 64 + 16 * j + t] >> (8 * g)) & 0xffu);
+#pragma unroll
+      for (int i = 0; i < 4; i++) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf, af[i], acc[i][j], 0, 0, 0, sw, 0, sa[i]);
+    }
+    __syncthreads();                                                  // every wave has read chunk c
+    store(st);
+    __syncthreads();
+  }
+
+  // lane (t, g): row m0 + 64 wm + 16 i + t, columns n0 + 64 wn + 16 j + 4 g .. + 3
+  const int nw = n0 + wn * 64;
+  float4 b4[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) b4[j] = p.bias ? *reinterpret_cast<const float4*>(p.bias + nw + 16 * j + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const long m = m0 + wm * 64 + 16 * i + t;
+    const bool live = m < M;
+    float r16[4][4];                                                  // the values as the operand type holds them
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      float v[4] = {acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w};
+      if (GELU) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] = gelu_tanh(v[r]);
+      }
+      const uint2 pk = pack_bf16x4(v[0], v[1], v[2], v[3]);
+      if (OUT16 && live) *reinterpret_cast<uint2*>(p.out16 + m * p.ld_out + nw + 16 * j + 4 * g) = pk;
+      if (OUTQ) {
+        unpack_bf16x2(pk.x, r16[j][0], r16[j][1]);
+        unpack_bf16x2(pk.y, r16[j][2], r16[j][3]);
+      }
+    }
+    if (OUTQ) {
+      // columns nw + 32 b .. + 31 of row m: MFMA tiles 2 b and 2 b + 1 on the four lanes that share t.  Every lane takes part in the exchanges.
+#pragma unroll
+      for (int b = 0; b < 2; b++) {
+        float amax = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; r++) amax = fmaxf(amax, fmaxf(fabsf(r16[2 * b][r]), fabsf(r16[2 * b + 1][r])));
+        amax = fmaxf(amax, __shfl_xor(amax, 16));
+        amax = fmaxf(amax, __shfl_xor(amax, 32));
+        const int x = mx_exponent(amax);
+        if (live) {
+#pragma unroll
+          for (int h = 0; h < 2; h++) {
+            const int j = 2 * b + h;
+            *reinterpret_cast<uint32_t*>(p.out_q + m * p.ld_outq + nw + 16 * j + 4 * g) = mx_codes4(r16[j][0], r16[j][1], r16[j][2], r16[j][3], x);
+          }
+          if (g == 0) p.out_e[m * p.ld_oute + (nw >> 5) + b] = (uint8_t)(x + 127);
+        }
+      }
+    }
+  }
+}
+
+struct F8Plan {
+  int gelu, out16, outq, m_tiles, n_tiles, grid;
+};
+
+// Every refusal of pxa_gemm_f8, before any HIP call; pxa_gemm_f8_plan runs the same code.
+int f8_plan(const pxa_gemm_f8_args* a, const char* who, F8Plan* pl) {
+  PXA_CHECK(a, "%s: null pointer (args)", who);
+  PXA_CHECK(a->M >= 1, "%s: M=%d must be at least 1", who, a->M);
+  PXA_CHECK(a->N >= 128 && a->N % 128 == 0, "%s: N=%d must be a positive multiple of 128", who, a->N);
+  PXA_CHECK(a->K >= 128 && a->K % 128 == 0, "%s: K=%d must be a positive multiple of 128", who, a->K);
+  PXA_CHECK(a->qa && a->ea && a->qw && a->ew, "%s: null pointer (qa, ea, qw, ew)", who);
+  PXA_CHECK(a->ldqa >= a->K && a->ldqa % 16 == 0 && a->ldqw >= a->K && a->ldqw % 16 == 0, "%s: ldqa=%ld, ldqw=%ld must be >= K and multiples of 16 (bytes)", who,
+            a->ldqa, a->ldqw);
+  PXA_CHECK(a->ldea >= a->K / 32 && a->ldea % 4 == 0 && a->ldew >= a->K / 32 && a->ldew % 4 == 0, "%s: ldea=%ld, ldew=%ld must be >= K / 32 and multiples of 4 (bytes)",
+            who, a->ldea, a->ldew);
+  PXA_CHECK(((uintptr_t)a->qa | (uintptr_t)a->qw) % 16 == 0, "%s: qa and qw must be 16-byte aligned", who);
+  PXA_CHECK(((uintptr_t)a->ea | (uintptr_t)a->ew) % 4 == 0, "%s: ea and ew must be 4-byte aligned", who);
+  PXA_CHECK(a->bias == nullptr || (uintptr_t)a->bias % 16 == 0, "%s: bias must be 16-byte aligned", who);
+  PXA_CHECK(a->act == 0 || a->act == 1, "%s: act=%d is not built (0 none, 1 GELU(tanh))", who, a->act);
+  PXA_CHECK(a->out16 || a->out_q, "%s: no output: at least one of out16 and out_q / out_e must be given", who);
+  PXA_CHECK((a->out_q != nullptr) == (a->out_e != nullptr), "%s: out_q and out_e go together", who);
+  if (a->out16) {
+    PXA_CHECK(a->ld_out >= a->N && a->ld_out % 8 == 0, "%s: ld_out=%ld must be >= N and a multiple of 8", who, a->ld_out);
+    PXA_CHECK((uintptr_t)a->out16 % 16 == 0, "%s: out16 must be 16-byte aligned", who);
+  }
+  if (a->out_q) {
+    PXA_CHECK(a->ld_outq >= a->N && a->ld_outq % 16 == 0, "%s: ld_outq=%ld must be >= N and a multiple of 16 (bytes)", who, a->ld_outq);
+    PXA_CHECK(a->ld_oute >= a->N / 32 && a->ld_oute % 4 == 0, "%s: ld_oute=%ld must be >= N / 32 and a multiple of 4 (bytes)", who, a->ld_oute);
+    PXA_CHECK((uintptr_t)a->out_q % 16 == 0, "%s: out_q must be 16-byte aligned", who);
+    PXA_CHECK((uintptr_t)a->out_e % 4 == 0, "%s: out_e must be 4-byte aligned", who);
+  }
+  pl->gelu = a->act == 1;
+  pl->out16 = a->out16 != nullptr;
+  pl->outq = a->out_q != nullptr;
+  pl->m_tiles = (a->M + F8_BM - 1) / F8_BM;
+  pl->n_tiles = a->N / F8_BN;
+  const long grid = (long)((pl->m_tiles + 7) / 8) * 8 * pl->n_tiles;
+  PXA_CHECK(grid <= 0x7fffffffL, "%s: M=%d, N=%d need more workgroups than a launch takes", who, a->M, a->N);
+  pl->grid = (int)grid;
+  return 0;
+}
+
+template <bool GELU>
+void f8_launch(const F8Plan& pl, hipStream_t stream, const F8Params& p) {
+  if (pl.out16 && pl.outq) hipLaunchKernelGGL((gemm_f8_kernel<GELU, true, true>), dim3(pl.grid), dim3(256), 0, stream, p);
+  else if (pl.out16) hipLaunchKernelGGL((gemm_f8_kernel<GELU, true, false>), dim3(pl.grid), dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((gemm_f8_kernel<GELU, false, true>), dim3(pl.grid), dim3(256), 0, stream, p);
+}
+
+int mx_rows_check(const char* who, long R, int K, long ld16, long ldq, long lde, const void* p16, const void* q, const void* e) {
+  PXA_CHECK(p16 && q && e, "%s: null pointer", who);
+  PXA_CHECK(R >= 1, "%s: bad R=%ld", who, R);
+  PXA_CHECK(K >= 32 && K % 32 == 0, "%s: K=%d must be a positive multiple of 32", who, K);
+  PXA_CHECK(ld16 >= K && ld16 % 8 == 0, "%s: ld=%ld must be >= K and a multiple of 8", who, ld16);
+  PXA_CHECK(ldq >= K && ldq % 16 == 0, "%s: ldq=%ld must be >= K and a multiple of 16 (bytes)", who, ldq);
+  PXA_CHECK(lde >= K / 32, "%s: lde=%ld must be >= K / 32", who, lde);
+  PXA_CHECK(((uintptr_t)p16 | (uintptr_t)q) % 16 == 0, "%s: the 16-bit / fp32 matrix and q must be 16-byte aligned", who);
+  return 0;
+}
+int mx_rows_grid(long R, int K) {
+  const long blocks = (R * (K / 16) + 255) / 256;
+  return (int)(blocks < 16384 ? blocks : 16384);
+}
+}  // namespace
+
+extern "C" int pxa_gemm_f8_plan(const pxa_gemm_f8_args* a, char* out, int out_len) {
+  F8Plan pl;
+  const int rc = f8_plan(a, "pxa_gemm_f8_plan", &pl);
+  if (rc) return rc;
+  PXA_CHECK(out && out_len > 0, "pxa_gemm_f8_plan: no output buffer");
+  snprintf(out, (size_t)out_len, "gemm_f8_kernel<%d,%d,%d> mfma=scale_16x16x128_f8f6f4 split=1 bm=%d bn=%d bk=%d m_tiles=%d n_tiles=%d grid=%d", pl.gelu, pl.out16,
+           pl.outq, F8_BM, F8_BN, F8_BK, pl.m_tiles, pl.n_tiles, pl.grid);
+  return 0;
+}
+
+extern "C" int pxa_gemm_f8(const pxa_gemm_f8_args* a, hipStream_t stream) {
+  F8Plan pl;
+  const int rc = f8_plan(a, "pxa_gemm_f8", &pl);
+  if (rc) return rc;
+  F8Params p;
+  p.qa = (const uint8_t*)a->qa; p.ldqa = a->ldqa; p.ea = (const uint8_t*)a->ea; p.ldea = a->ldea;
+  p.qw = (const uint8_t*)a->qw; p.ldqw = a->ldqw; p.ew = (const uint8_t*)a->ew; p.ldew = a->ldew;
+  p.M = a->M; p.N = a->N; p.K = a->K;
+  p.bias = a->bias;
+  p.out16 = (bf16_t*)a->out16; p.ld_out = a->ld_out;
+  p.out_q = (uint8_t*)a->out_q; p.ld_outq = a->ld_outq; p.out_e = (uint8_t*)a->out_e; p.ld_oute = a->ld_oute;
+  p.m_tiles = pl.m_tiles; p.n_tiles = pl.n_tiles;
+  if (pl.gelu) f8_launch<true>(pl, stream, p);
+  else f8_launch<false>(pl, stream, p);
+  PXA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pxa_mx_quant_rows(const void* src, int src_is_f32, long ld, long R, int K, void* q, long ldq, void* e, long lde, hipStream_t stream) {
+  const int rc = mx_rows_check("pxa_mx_quant_rows", R, K, ld, ldq, lde, src, q, e);
+  if (rc) return rc;
+  const int grid = mx_rows_grid(R, K);
+  if (src_is_f32) hipLaunchKernelGGL(mx_quant_rows_kernel<true>, dim3(grid), dim3(256), 0, stream, src, ld, R, K, (uint8_t*)q, ldq, (uint8_t*)e, lde);
+  else hipLaunchKernelGGL(mx_quant_rows_kernel<false>, dim3(grid), dim3(256), 0, stream, src, ld, R, K, (uint8_t*)q, ldq, (uint8_t*)e, lde);
+  PXA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pxa_mx_dequant_rows(const void* q, long ldq, const void* e, long lde, long R, int K, void* dst16, long ld, hipStream_t stream) {
+  const int rc = mx_rows_check("pxa_mx_dequant_rows", R, K, ld, ldq, lde, dst16, q, e);
+  if (rc) return rc;
+  hipLaunchKernelGGL(mx_dequant_rows_kernel, dim3(mx_rows_grid(R, K)), dim3(256), 0, stream, (const uint8_t*)q, ldq, (const uint8_t*)e, lde, R, K, (bf16_t*)dst16, ld);
+  PXA_LAUNCH_CHECK();
+  return 0;
+}

@@ -239,6 +239,10 @@ class Engine:
         # unchanged on the merged operands, and the backward computes adapter gradients only: the base model is frozen.
         self.lora = None
         self._lora_refs = ()
+        # FP8 inference (enable_fp8): None = the 16-bit engine, whose launches are exactly those of tests/golden/engine_schedule_*.txt.
+        self.fp8 = None
+        self._f8 = None
+        self._f8_ref = None
 
     # ------------------------------------------------------------------ helpers
     def pos_table(self, h, w):
@@ -318,6 +322,9 @@ class Engine:
         """lora: lora.LoraAdapters with its ParamStore built on this engine's device.  From here on every bump of either store re-merges: the base store's
         re-cast (refresh_shadow) wipes the merge and is followed by it; an adapter update (optimizer step, re-cast of edited adapters) bumps the base store, so
         the generation that keys Engine._text_cache moves and the shadow / prescaled copy are rewritten in place under any captured graph."""
+        if self.fp8 is not None:
+            raise RuntimeError("FP8 inference is on: adapters cannot be attached to it (disable_fp8() first, or merge_and_unload() the adapters and enable FP8 "
+                               "on the merged weights)")
         self.detach_lora(remerge=False)
         self.lora = lora
         self._lora_refs = (weakref.WeakMethod(self._lora_merge), weakref.WeakMethod(self._lora_changed))
@@ -401,6 +408,62 @@ class Engine:
         Nk = kc.shape[1]
         return SelfKV(kc, vc, Nk, (Nk * D, D, self.head_dim), bwd, zero)
 
+    # ------------------------------------------------------------------ FP8 inference (MXFP8 token GEMMs, csrc/gemm_f8.hip)
+    F8_LINEARS = ("attn.qkv", "attn.proj", "cross_attn.q_linear", "cross_attn.proj", "mlp.fc1", "mlp.fc2")
+
+    def enable_fp8(self, gemm="mx"):
+        """Opt-in W8A8 inference: the six token GEMMs of every block take MXFP8 operands (e4m3fn, one E8M0 scale per 32 k).  gemm="mx": ops.gemm_f8 on the
+        block-scaled K = 128 MFMA; gemm="dequant": the same quantised operands, dequantised exactly and multiplied by ops.gemm - the reference / A/B mode.
+        The MX copies of the weights are allocated once, quantised from the 16-bit operands (attn.qkv from the q-prescaled copy where prescaling is on) and
+        rewritten in place behind _refresh_qs at every ParamStore.bump, so a captured sampling graph reads current FP8 weights after a weight load or an
+        optimizer step.  The fp32 masters and the 16-bit shadow are untouched.  kv_linear, the caption MLP, the embedders and the final layer stay 16-bit."""
+        if gemm not in ("mx", "dequant"):
+            raise ValueError(f"enable_fp8: gemm={gemm!r} is not one of 'mx', 'dequant'")
+        if self.lora is not None:
+            raise RuntimeError("FP8 inference with LoRA adapters attached is not built: call merge_and_unload() first, then enable_fp8()")
+        S, depth = self.S, self.cfg["depth"]
+        if self._f8 is None:
+            self._f8 = {}
+            for name in self.F8_LINEARS:
+                N, K = S.shape[f"blocks.0.{name}.weight"]
+                self._f8[name] = (torch.empty((depth, N, K), dtype=torch.float8_e4m3fn, device=S.device), torch.empty((depth, N, K // 32), dtype=torch.uint8, device=S.device))
+        if self._f8_ref is None:
+            self._f8_ref = weakref.WeakMethod(self._refresh_f8)
+            S._on_change.append(self._f8_ref)              # behind _refresh_qs: attn.qkv is quantised from the copy that one has just rewritten
+        self.fp8 = gemm
+        self._text_cache = None
+        self._refresh_f8()
+
+    def disable_fp8(self):
+        """Back to the 16-bit launches.  The MX buffers stay allocated (a later enable_fp8 rewrites them at the same addresses) but are no longer refreshed."""
+        if self._f8_ref is not None and self._f8_ref in self.S._on_change:
+            self.S._on_change.remove(self._f8_ref)
+        self._f8_ref = None
+        self.fp8 = None
+
+    def _refresh_f8(self):
+        """Re-quantise the MX weight copies from the 16-bit operands, in place."""
+        S, depth = self.S, self.cfg["depth"]
+        for name in self.F8_LINEARS:
+            q, e = self._f8[name]
+            if name == "attn.qkv" and self._qs is not None:  # one launch: the prescaled copies of all blocks are one matrix
+                ops.mx_quant_rows(self._qs[0].view(-1, q.shape[2]), q=q.view(-1, q.shape[2]), e=e.view(-1, e.shape[2]))
+                continue
+            for l in range(depth):
+                ops.mx_quant_rows(S.w(f"blocks.{l}.{name}.weight"), q=q[l], e=e[l])
+
+    def _lin_f8(self, x, l, name, act=ops.ACT_NONE, mx_out=False):
+        """Linear `name` of block l on MXFP8 operands.  x: a 16-bit matrix (quantised here) or an (q, e) pair a previous GEMM left.  mx_out: return the result
+        as an (q, e) pair - from the GEMM's own epilogue in 'mx' mode."""
+        S = self.S
+        wq, we = self._f8[name]
+        bias = self._qs[1][l] if name == "attn.qkv" and self._qs is not None else S.f(f"blocks.{l}.{name}.bias")
+        xq, xe = x if isinstance(x, tuple) else ops.mx_quant_rows(x)
+        if self.fp8 == "mx":
+            return ops.gemm_f8(xq, xe, wq[l], we[l], bias=bias, act=act, out16=not mx_out, mx=mx_out)
+        y = ops.gemm(ops.mx_dequant_rows(xq, xe), ops.mx_dequant_rows(wq[l], we[l]), NT, bias=bias, act=act, descending=self._desc(name))
+        return ops.mx_quant_rows(y) if mx_out else y
+
     def block_fwd(self, l, x_prev, u_prev, gate_prev, ctx):
         """Returns (x2, u3, gate_mlp, saved).  x_prev/u_prev/gate_prev: residual, pending gated branch of the previous block."""
         S, c = self.S, self.cfg
@@ -412,7 +475,10 @@ class Engine:
         r = ops.ln_mod_fwd(x_prev, sm, scm, st, u=u_prev, gate=gate_prev, gate_stride=st, rows_per_batch=N, want_stats=True)
         x_in, xn1, mean1, rstd1 = r["x"], r["xn"], r["mean"], r["rstd"]
         pre = dict(q_prescaled=True) if self.prescale else {}
-        if self.prescale:           # block l's views of the engine's persistent copy: weight (3D, D), bias (3D,) with the q rows times scale * log2 e
+        f8 = self.fp8 is not None   # FP8 inference (enable_fp8; Engine.forward refuses it with a backward to feed): the six token GEMMs go through _lin_f8
+        if f8:
+            qkv = self._lin_f8(xn1, l, "attn.qkv")
+        elif self.prescale:         # block l's views of the engine's persistent copy: weight (3D, D), bias (3D,) with the q rows times scale * log2 e
             qkv = ops.gemm(xn1, self._qs[0][l], NT, bias=self._qs[1][l], descending=True)
         else:
             qkv = self._lin(xn1, p + "attn.qkv")
@@ -424,10 +490,10 @@ class Engine:
         lse = torch.empty((B, H, N), dtype=F32, device=qkv.device)
         skv = self._self_kv(l, qkv, ctx)
         ops.attention_fwd(qkv[:, :D], skv.k, skv.v, a, lse, B, H, N, skv.Nk, ((N * 3 * D, 3 * D, self.head_dim), skv.sk, skv.sk, (N * D, D, self.head_dim)), **pre)
-        u1 = self._lin(a, p + "attn.proj")
+        u1 = self._lin_f8(a, l, "attn.proj") if f8 else self._lin(a, p + "attn.proj")
         r = ops.ln_mod_fwd(x_in, u=u1, gate=gm, gate_stride=st, want_xn=False, want_xb=True, rows_per_batch=N)
         x1, x1b = r["x"], r["xb"]
-        qc = self._lin(x1b, p + "cross_attn.q_linear")
+        qc = self._lin_f8(x1b, l, "cross_attn.q_linear") if f8 else self._lin(x1b, p + "cross_attn.q_linear")
         kvc = ctx.kvc[l] if ctx.kvc is not None else None      # inference: constant over the sampler's steps (Engine._text_cache)
         if kvc is None:
             kvc = self._lin(ctx.ye, p + "cross_attn.kv_linear")
@@ -437,16 +503,19 @@ class Engine:
         lse_c = torch.empty((B, H, N), dtype=F32, device=qkv.device)
         ops.attention_fwd(qc, kvc[:, :D], kvc[:, D:], cr, lse_c, B, H, N, ctx.max_len, self._cross_strides(N),
                           kv_start=ctx.kv_start, kv_len=ctx.kv_len, max_kv_len=ctx.max_len, kv_len_host=ctx.lens_host)
-        u2 = self._lin(cr, p + "cross_attn.proj")
+        u2 = self._lin_f8(cr, l, "cross_attn.proj") if f8 else self._lin(cr, p + "cross_attn.proj")
         r = ops.ln_mod_fwd(x1, sl, scl, st, u=u2, x_out=x1, rows_per_batch=N, want_stats=True)
         x2, xn2, mean2, rstd2 = r["x"], r["xn"], r["mean"], r["rstd"]
-        if ctx.need_grad_aux:
+        if f8:                                     # h leaves fc1 as MXFP8, an (q, e) pair from the GEMM's own epilogue: no pass between fc1 and fc2
+            hpre = None
+            h = self._lin_f8(xn2, l, "mlp.fc1", act=ops.ACT_GELU, mx_out=True)
+        elif ctx.need_grad_aux:
             hpre = torch.empty((B * N, S.shape[p + "mlp.fc1.weight"][0]), dtype=BF16, device=qkv.device)
             h = self._lin(xn2, p + "mlp.fc1", act=ops.ACT_GELU_SAVE_GRAD, out2=hpre)   # hpre holds GELU'(pre-activation), bf16
         else:                                      # inference / the discarded forward of a checkpointed step: no backward reads GELU' - one output, half the
             hpre = None                            # epilogue's transcendentals and stores
             h = self._lin(xn2, p + "mlp.fc1", act=ops.ACT_GELU)
-        u3 = self._lin(h, p + "mlp.fc2")
+        u3 = self._lin_f8(h, l, "mlp.fc2") if f8 else self._lin(h, p + "mlp.fc2")
         saved = BlockSaved(x_in=x_in, mean1=mean1, rstd1=rstd1, xn1=xn1, qkv=qkv, a=a, lse=lse, u1=u1, x1b=x1b, qc=qc, kvc=kvc,
                            cr=cr, lse_c=lse_c, x2=x2, mean2=mean2, rstd2=rstd2, xn2=xn2, hpre=hpre, h=h, u3=u3, skv=skv, qkn=qkn)
         return x2, u3, gl, saved
@@ -561,6 +630,9 @@ class Engine:
         B, _, Hl, Wl = x.shape
         h, w = Hl // 2, Wl // 2
         N, D, depth = h * w, c["hidden_size"], c["depth"]
+        if self.fp8 is not None and (save or torch.is_grad_enabled()):
+            raise RuntimeError("FP8 inference is on (enable_fp8): a forward that keeps activations for a backward is not built - run it under torch.no_grad(), "
+                               "or disable_fp8() before training")
         ctx = self.step_ctx(B, N, (h, w), mod, lens)
         ctx.need_grad_aux = save == "all"
         L = y.shape[0] // B

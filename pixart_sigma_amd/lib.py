@@ -13,7 +13,7 @@ OPERAND = os.environ.get("PXA_OPERAND_DTYPE", "bf16").lower()
 assert OPERAND in ("bf16", "f16"), f"PXA_OPERAND_DTYPE must be bf16 or f16, got {OPERAND!r}"
 OPERAND_DTYPE = torch.float16 if OPERAND == "f16" else torch.bfloat16
 LIB_PATH = os.environ.get("PXA_LIB_PATH") or os.path.join(_HERE, "libpixart_hip_f16.so" if OPERAND == "f16" else "libpixart_hip.so")   # env override: A/B kernel builds
-ABI_VERSION = 11      # the LoRA entry points (pxa_lora_merge / pxa_lora_bwd / pxa_lora_bwd_ws_bytes) and the image ones (pxa_image_*) are additions under the same number, as is pxa_vae_posterior: tests/test_vae_attn_host.py pins 11
+ABI_VERSION = 11      # the LoRA entry points (pxa_lora_merge / pxa_lora_bwd / pxa_lora_bwd_ws_bytes) and the image ones (pxa_image_*) are additions under the same number, as are pxa_vae_posterior and the MXFP8 ones (pxa_mx_* / pxa_gemm_f8*): tests/test_vae_attn_host.py pins 11
 
 c_void_p, c_int, c_long, c_float = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -84,6 +84,13 @@ class GemmW8Args(C.Structure):
                 ("aux", c_void_p), ("ldaux", c_long), ("out16", c_void_p), ("ld_out", c_long), ("out_f32", c_void_p), ("ld_f32", c_long)]
 
 
+class GemmF8Args(C.Structure):
+    """pxa_gemm_f8_args (include/pixart_hip.h, MXFP8 inference GEMMs of the denoiser)."""
+    _fields_ = [("qa", c_void_p), ("ldqa", c_long), ("ea", c_void_p), ("ldea", c_long), ("qw", c_void_p), ("ldqw", c_long), ("ew", c_void_p), ("ldew", c_long),
+                ("M", c_int), ("N", c_int), ("K", c_int), ("act", c_int), ("bias", c_void_p),
+                ("out16", c_void_p), ("ld_out", c_long), ("out_q", c_void_p), ("ld_outq", c_long), ("out_e", c_void_p), ("ld_oute", c_long)]
+
+
 # name -> argtypes (all return int); must list every symbol include/pixart_hip.h declares
 _P, _I, _L, _F = c_void_p, c_int, c_long, c_float
 _G = C.POINTER(GridArg)
@@ -134,6 +141,9 @@ SIGNATURES = {
     "pxa_fp8_quant_rows": [_P, _I, _L, _I, _I, _P, _L, _P, _P],
     "pxa_fp8_dequant_rows": [_P, _L, _P, _I, _I, _P, _L, _P],
     "pxa_gemm_w8": [C.POINTER(GemmW8Args), _P],
+    "pxa_mx_quant_rows": [_P, _I, _L, _L, _I, _P, _L, _P, _L, _P],
+    "pxa_mx_dequant_rows": [_P, _L, _P, _L, _L, _I, _P, _L, _P],
+    "pxa_gemm_f8": [C.POINTER(GemmF8Args), _P],
     "pxa_lora_merge": [_P, _L, _I, _I, _I, _P, _P, _L, _I, _F, _P, _L, _P, _L, _I, _I, _F, _P, _P],
     "pxa_lora_bwd": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "pxa_image_resample": [_P, _L, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P],
@@ -143,7 +153,7 @@ SIGNATURES = {
 }
 OTHER_SYMBOLS = ["pxa_last_error", "pxa_abi_version", "pxa_operand_dtype", "pxa_device_info", "pxa_gemm_splitk_ws_elems", "pxa_came_scratch_elems", "pxa_attn_bwd_stats_bytes", "pxa_gemm_set_dynamic_items", "pxa_gemm_plan", "pxa_attn_plan",
                  "pxa_mfma_rate_probe_bytes", "pxa_mfma_rate_probe", "pxa_lora_bwd_ws_bytes", "pxa_image_resample_ws_bytes", "pxa_vae_posterior",
-                 "pxa_gemm_w8_plan", "pxa_gemm_w8_max_m"]
+                 "pxa_gemm_w8_plan", "pxa_gemm_w8_max_m", "pxa_gemm_f8_plan"]
 
 _lib = None
 
@@ -175,6 +185,7 @@ def load():
     lib.pxa_lora_bwd_ws_bytes.argtypes, lib.pxa_lora_bwd_ws_bytes.restype = [c_long, c_int, c_int, c_int], c_long
     lib.pxa_image_resample_ws_bytes.argtypes, lib.pxa_image_resample_ws_bytes.restype = [c_int, c_int], c_long
     lib.pxa_gemm_w8_plan.argtypes, lib.pxa_gemm_w8_plan.restype = [C.POINTER(GemmW8Args), C.c_char_p, c_int], c_int
+    lib.pxa_gemm_f8_plan.argtypes, lib.pxa_gemm_f8_plan.restype = [C.POINTER(GemmF8Args), C.c_char_p, c_int], c_int
     lib.pxa_gemm_w8_max_m.argtypes, lib.pxa_gemm_w8_max_m.restype = [], c_int
     lib.pxa_mfma_rate_probe_bytes.argtypes, lib.pxa_mfma_rate_probe_bytes.restype = [], c_long
     # bound here and not in SIGNATURES: tests/test_vae_kernel_forms_gpu.py holds the pxa_vae_* entries of SIGNATURES against its own list of refused calls

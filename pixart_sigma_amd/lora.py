@@ -190,6 +190,9 @@ def add_lora(model, config=None, **kw):
         config = LoraConfig(**kw)
     elif kw:
         raise TypeError("add_lora takes a LoraConfig or its fields, not both")
+    if getattr(model, "fp8", None) is not None:
+        raise RuntimeError("FP8 inference is on: adapters cannot be attached to it (disable_fp8() first, or merge_and_unload() the adapters and enable FP8 on "
+                           "the merged weights)")
     if getattr(model, "_lora", None) is not None:
         raise RuntimeError("the model already carries LoRA adapters: merge_and_unload() first")
     model._lora = LoraAdapters(model, config)

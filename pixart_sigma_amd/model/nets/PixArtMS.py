@@ -292,6 +292,7 @@ class PixArtMS(nn.Module):
         self.final_layer = T2IFinalLayer(hidden_size, patch_size, self.out_channels)
         self._store = self._engine = None
         self._lora = None                 # lora.LoraAdapters once add_lora / load_lora attached adapters (not a submodule: the base parameter list stays as it is)
+        self._fp8 = None                  # "mx" / "dequant" once enable_fp8 switched the blocks' token GEMMs to MXFP8 (inference only)
         self._anchor = None
         self._mask_cache = {}
         self.initialize()
@@ -383,8 +384,35 @@ class PixArtMS(nn.Module):
             self._engine = Engine(self._store, cfg)
             self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self._store.refresh_shadow()
+        if self._engine.fp8 != self._fp8:      # a store / engine built after enable_fp8 (the model moved): the MX weight copies follow it
+            self._engine.enable_fp8(self._fp8) if self._fp8 is not None else self._engine.disable_fp8()
         if self._lora is not None:       # behind the base re-cast: the merge reads both fp32 masters and rewrites the adapted rows of the shadow
             self._lora.prepare(self, device)
+
+    # ---- FP8 inference (engine.Engine.enable_fp8; csrc/gemm_f8.hip)
+    @property
+    def fp8(self):
+        """None, "mx" or "dequant"."""
+        return self._fp8
+
+    def enable_fp8(self, gemm="mx"):
+        """Opt-in W8A8 inference: attn.qkv / attn.proj / cross_attn.q_linear / cross_attn.proj / mlp.fc1 / mlp.fc2 of every block run on MXFP8 operands
+        (e4m3fn elements, one power-of-two scale per 32 k, activations quantised on the fly).  gemm="mx": the block-scaled FP8 MFMA GEMM; gemm="dequant": the
+        same quantised operands through the 16-bit GEMM (reference / A/B mode).  Forwards must run under torch.no_grad(); adapters must be merged first."""
+        if gemm not in ("mx", "dequant"):
+            raise ValueError(f"enable_fp8: gemm={gemm!r} is not one of 'mx', 'dequant'")
+        if self._lora is not None:
+            raise RuntimeError("FP8 inference with LoRA adapters attached is not built: call merge_and_unload() first, then enable_fp8()")
+        self._fp8 = gemm
+        if self._engine is not None:
+            self._engine.enable_fp8(gemm)
+        return self
+
+    def disable_fp8(self):
+        self._fp8 = None
+        if self._engine is not None:
+            self._engine.disable_fp8()
+        return self
 
     # ---- LoRA adapters (lora.py; the reference's peft calls, train_scripts/train_pixart_lora_hf.py:505-524,552,990)
     def add_lora(self, config=None, **kw):
@@ -416,6 +444,8 @@ class PixArtMS(nn.Module):
         """x: (N, C, H, W) latent; timestep: (N,); y: (N, 1, L, C_caption); mask: (N, L) | (N,1,1,L) | None.
         Returns (N, 2C, H, W) fp32."""
         assert x.is_cuda, "pixart_sigma_amd.PixArtMS runs on the MI355X HIP kernels only (no CPU path; use oracle/ for CPU checks)"
+        if self._fp8 is not None and torch.is_grad_enabled():
+            raise RuntimeError("FP8 inference is on (enable_fp8): run the forward under torch.no_grad(), or disable_fp8() before training")
         dev = x.device
         self._prepare(dev)
         bs = x.shape[0]

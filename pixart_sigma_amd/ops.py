@@ -804,6 +804,101 @@ def gemm_w8_plan(a, q, scale, act=ACT_NONE, aux=None, out=None, out_f32=None):
     return buf.value.decode()
 
 
+# ------------------------------------------------------------------------------------------------ MXFP8 (e4m3fn + one E8M0 scale per 32 k) for denoiser inference
+U8 = torch.uint8
+
+
+def _chk_mx(q, e, name, cuda=True):
+    assert (q.is_cuda or not cuda) and q.dtype == FP8 and q.dim() == 2 and q.stride(1) == 1, f"{name}: q needs a 2-D contiguous-last-dim float8_e4m3fn CUDA tensor"
+    assert q.shape[1] % 32 == 0, f"{name}: K={q.shape[1]} must be a multiple of 32"
+    _chk(e, U8, f"{name} scales", cuda=cuda)
+    assert tuple(e.shape) == (q.shape[0], q.shape[1] // 32), f"{name}: e needs ({q.shape[0]}, {q.shape[1] // 32}) uint8, got {tuple(e.shape)}"
+
+
+def mx_quant_rows(x, q=None, e=None):
+    """The project's MXFP8 quantiser (pxa_mx_quant_rows): x (R, K) of the operand type or fp32, K % 32 == 0 -> (q (R, K) float8_e4m3fn, e (R, K / 32) uint8, E8M0)
+    with, per block of 32 consecutive k, X = ceil(log2(amax / 448)) (0 for an all-zero block, clamped to [-127, 127]), e = X + 127, q = e4m3fn(x / 2^X)."""
+    assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in (BF16, F32), f"mx_quant_rows: need a 2-D CUDA tensor of {BF16} or fp32, got {x.dtype}"
+    R, K = x.shape
+    assert K % 32 == 0, f"mx_quant_rows: K={K} must be a multiple of 32"
+    if q is None:
+        q = torch.empty(R, K, dtype=FP8, device=x.device)
+    if e is None:
+        e = torch.empty(R, K // 32, dtype=U8, device=x.device)
+    _chk_mx(q, e, "mx_quant_rows")
+    assert tuple(q.shape) == (R, K)
+    call("pxa_mx_quant_rows", ptr(x), int(x.dtype == F32), x.stride(0), R, K, ptr(q), q.stride(0), ptr(e), e.stride(0))
+    return q, e
+
+
+def mx_dequant_rows(q, e, out=None):
+    """out[r][k] = q[r][k] * 2^(e[r][k / 32] - 127) in the operand type (pxa_mx_dequant_rows): the exact inverse of mx_quant_rows' scaling."""
+    _chk_mx(q, e, "mx_dequant_rows")
+    R, K = q.shape
+    if out is None:
+        out = torch.empty(R, K, dtype=BF16, device=q.device)
+    _chk(out, BF16, "out")
+    assert tuple(out.shape) == (R, K)
+    call("pxa_mx_dequant_rows", ptr(q), q.stride(0), ptr(e), e.stride(0), R, K, ptr(out), out.stride(0))
+    return out
+
+
+def _gemm_f8_args(plan, qa, ea, qw, ew, bias, act, out, out_q, out_e, out16, mx):
+    def ptr(t):                    # the plan entry tests alignment: a 16-byte aligned address stands for a buffer gemm_f8 would allocate
+        return C.c_void_p((C.addressof(_W8_SOMEWHERE) + 15) & ~15) if isinstance(t, _Unallocated) else lib.ptr(t, cuda=not plan)
+    _chk_mx(qa, ea, "gemm_f8: A", cuda=not plan)
+    _chk_mx(qw, ew, "gemm_f8: W", cuda=not plan)
+    M, K = qa.shape
+    N, K2 = qw.shape
+    assert K == K2, f"gemm_f8: K mismatch {K} vs {K2}"
+    g = lib.GemmF8Args()
+    g.qa, g.ldqa, g.ea, g.ldea = ptr(qa), qa.stride(0), ptr(ea), ea.stride(0)
+    g.qw, g.ldqw, g.ew, g.ldew = ptr(qw), qw.stride(0), ptr(ew), ew.stride(0)
+    g.M, g.N, g.K, g.act = M, N, K, act
+    if bias is not None:
+        _chk(bias, F32, "bias", cuda=not plan)
+        assert bias.numel() == N
+        g.bias = ptr(bias)
+    assert (out_q is None) == (out_e is None), "gemm_f8: out_q and out_e go together"
+    if out16 or out is not None:
+        if out is None:
+            out = _Unallocated(M, N, BF16) if plan else torch.empty((M, N), dtype=BF16, device=qa.device)
+        if not isinstance(out, _Unallocated):
+            _chk(out, BF16, "out", cuda=not plan)
+        assert tuple(out.shape) == (M, N)
+        g.out16, g.ld_out = ptr(out), out.stride(0)
+    if mx or out_q is not None:
+        if out_q is None:
+            out_q = _Unallocated(M, N, FP8) if plan else torch.empty((M, N), dtype=FP8, device=qa.device)
+            out_e = _Unallocated(M, N // 32, U8) if plan else torch.empty((M, N // 32), dtype=U8, device=qa.device)
+        if not isinstance(out_q, _Unallocated):
+            _chk_mx(out_q, out_e, "gemm_f8: out", cuda=not plan)
+        assert tuple(out_q.shape) == (M, N)
+        g.out_q, g.ld_outq, g.out_e, g.ld_oute = ptr(out_q), out_q.stride(0), ptr(out_e), out_e.stride(0)
+    return g, out, out_q, out_e
+
+
+def gemm_f8(qa, ea, qw, ew, bias=None, act=ACT_NONE, out=None, out_q=None, out_e=None, out16=True, mx=False):
+    """act(sum_k A[m][k] W[n][k] + bias[n]) with both operands in MXFP8 on the block-scaled K = 128 MFMA (pxa_gemm_f8).  A = (qa (M, K), ea (M, K / 32)),
+    W = (qw (N, K), ew (N, K / 32)); N and K multiples of 128; bias (N,) fp32 or None; act ACT_NONE or ACT_GELU.  out16: write the 16-bit result (`out`, allocated
+    if not given); mx (or out_q / out_e given): also, or only, write that 16-bit-rounded result quantised along N by mx_quant_rows' rule.  Returns `out` where only
+    the 16-bit result is asked for, (out_q, out_e) where only the quantised one is, (out, out_q, out_e) for both."""
+    g, out, out_q, out_e = _gemm_f8_args(False, qa, ea, qw, ew, bias, act, out, out_q, out_e, out16, mx)
+    call("pxa_gemm_f8", C.byref(g))
+    if out_q is None:
+        return out
+    return (out_q, out_e) if out is None else (out, out_q, out_e)
+
+
+def gemm_f8_plan(qa, ea, qw, ew, bias=None, act=ACT_NONE, out=None, out_q=None, out_e=None, out16=True, mx=False):
+    """pxa_gemm_f8_plan's line for the call gemm_f8 would make (kernel instance, tile, grid); raises what gemm_f8 would raise for a call the library refuses.
+    Needs no GPU: the tensors may live on any device."""
+    g, *_ = _gemm_f8_args(True, qa, ea, qw, ew, bias, act, out, out_q, out_e, out16, mx)
+    buf = C.create_string_buffer(256)
+    lib.check(lib.load().pxa_gemm_f8_plan(C.byref(g), buf, len(buf)), "pxa_gemm_f8_plan")
+    return buf.value.decode()
+
+
 def vae_nchw_to_grid(img, y, mul=1.0):
     _chk(img, F32, "image")
     assert img.is_contiguous() and img.shape[0] == y.B and img.shape[2] == y.H and img.shape[3] == y.W

@@ -57,6 +57,9 @@ def get_args():
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the whole process (reference: fp16)")
     p.add_argument("--lora_path", default=None, type=str, help="peft-format adapter directory (adapter_config.json + adapter_model.safetensors) for the transformer blocks")
     p.add_argument("--lora_scale", default=1.0, type=float, help="multiplies the adapters' lora_alpha / r (0 = the base model)")
+    p.add_argument("--dit_fp8", nargs="?", const="mx", default=None, choices=["mx", "dequant"],
+                   help="run the six token GEMMs of every denoiser block on MXFP8 operands (PixArtMS.enable_fp8): mx = the block-scaled FP8 MFMA GEMM, "
+                        "dequant = the same quantised operands through the 16-bit GEMM (A/B reference).  Adapters of --lora_path are merged first")
     p.add_argument("--load_ema", action="store_true", help="with --model_path: sample from the checkpoint's state_dict_ema (written by train.py --ema)")
     p.add_argument("--save_images", default=None, choices=["png", "jpg"], help="also write one picture per sample (as the reference's save_image: output/<save_name>/<index>.<ext>)")
     return p.parse_args()
@@ -136,6 +139,11 @@ def main():
         lo = model.load_lora(args.lora_path, scale=args.lora_scale)
         print(f"LoRA adapters from {args.lora_path}: r={lo.config.r}, s={lo.scale:g}, {len(lo.params) // 2} adapted linears")
     model = model.to(dev).eval()
+    if args.dit_fp8:
+        if args.lora_path:              # FP8 quantises the merged weights: there is no adapter path beside an FP8 GEMM
+            model.merge_and_unload()
+        model.enable_fp8(args.dit_fp8)
+        print(f"denoiser token GEMMs on MXFP8 operands ({args.dit_fp8})")
     from pixart_sigma_amd.vae import AutoencoderKL
     vae_dir = "output/pretrained_models/sd-vae-ft-ema" if args.sdvae else f"{args.pipeline_load_from}/vae"    # reference inference.py:191-196
     vae = None
