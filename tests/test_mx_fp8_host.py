@@ -76,6 +76,38 @@ def test_reference_round_trip_is_exact_on_the_grid(dtype):
     assert (q1.float() == q0.view(FP8).float()).all()
 
 
+def test_code_table_matches_torch():
+    b = R.finite_codes()
+    assert b.numel() == 254 and 0x80 in b.tolist() and 0x7F not in b.tolist() and 0xFF not in b.tolist()
+    assert (R.code_values(b) == b.view(FP8).double()).all()
+    assert R.code_values(torch.tensor([0x01, 0x7E, 0xFE], dtype=torch.uint8)).tolist() == [2.0 ** -9, 448.0, -448.0]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_reference_rounds_ties_to_even(dtype):
+    mid, want = R.tie_midpoints()
+    assert mid.numel() == 252 and ((want & 1) == 0).all() and mid[0] == 2.0 ** -10 and mid[125] == 432.0
+    x, q_want, e_want = R.tie_rows()
+    assert (x.to(dtype).double() == x.double()).all(), f"a midpoint is not exact in {dtype}"
+    for m, w in zip(mid.tolist(), want.tolist()):                # every midpoint is in every row, at its expected code
+        hit = x[0] == m
+        assert hit.sum() == 1 and q_want[0][hit].item() == w
+    q, e = R.quant_rows(x.to(dtype))
+    assert (e == e_want).all()
+    bad = q.view(torch.uint8) != q_want
+    assert not bad.any(), f"{bad.sum().item()} ties do not go to the even code; first {x[bad][0].item()} -> {q.view(torch.uint8)[bad][0].item():#x}"
+
+
+def test_reference_exponent_edges_by_hand():
+    x, X = R.exponent_edge_rows()
+    assert (R.exponents(x) == X[:, None]).all(), (R.exponents(x)[:, 0] - X).tolist()
+    q, e = R.quant_rows(x)
+    assert (e.long() == X[:, None] + 127).all() and e.min() == 0
+    assert not ((q.view(torch.uint8) & 0x7F) == 0x7F).any()
+    at = (q[:, 5].float().abs(), q[:, 52].float().abs())
+    assert ((at[0] >= 224) | (X == -127)).all() and (at[0] <= 448).all() and (at[0] == at[1]).all()
+
+
 # ------------------------------------------------------------------------------------------------ the library's plan entry
 def _operands(M, N, K):
     return (torch.zeros(M, K, dtype=torch.uint8).view(FP8), torch.zeros(M, K // 32, dtype=torch.uint8),
